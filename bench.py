@@ -23,6 +23,11 @@ starts N fresh rank processes of this same script — one per GPU, like the refe
 ``benchmark-run.sh`` → ``flink run`` at the cluster's parallelism — and exits with their status.
 Under ``python -m torch.distributed.run --nproc-per-node N … bench.py --gpus N`` the ranks come
 from the environment, and a ``WORLD_SIZE`` that differs from ``--gpus`` is an error.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the ``--steps`` timed
+rounds, and one JSON result line. ``--dump-outputs DIR`` also writes the coefficients the timed
+path ends with to ``DIR/coefficients.npy`` (the data is seeded, so two builds can be compared).
+``--full`` is where measurements and checks beyond the headline figure belong.
 """
 from __future__ import annotations
 
@@ -106,6 +111,26 @@ def verify_exchange(make, comm, rounds: int = VERIFY_ROUNDS):
     rel = float((ca - cb).abs().max()) / scale
     ok = comm.all_agree(bool(identical and rel <= VERIFY_RTOL))
     return ok, {"replicas_identical": identical, "rel_err_vs_process_group": rel}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, trainer) -> dict:
+    """Writes what a caller of the timed path receives after its last step — the model
+    coefficients as ``DeviceGlmTrainer.fit()`` returns them (fp64, the model's width), read after
+    ``flush()`` — to ``directory/coefficients.npy``. A model wider than DUMP_MAX_BYTES allows is
+    cut to a fixed, seeded sample of its entries (ascending positions, the same in every run).
+    Returns {name: shape}."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    coef = trainer.coef[:trainer.d_model].to(torch.float64).cpu().numpy()
+    most = DUMP_MAX_BYTES // coef.itemsize
+    if coef.size > most:
+        coef = coef[np.sort(np.random.default_rng(0).choice(coef.size, size=most, replace=False))]
+    np.save(os.path.join(directory, "coefficients.npy"), coef)
+    return {"coefficients": list(coef.shape)}
 
 
 def launch_ranks(n: int, argv, env=None, timeout: float = None) -> int:
@@ -198,9 +223,19 @@ def main():
                          "idles through the host-side capture right before the timed region)")
     ap.add_argument("--torch-profile", default="", help="after the timed region, record a torch.profiler trace of "
                                                         "extra rounds into this directory (not timed)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step (the model "
+                         "coefficients) to DIR/<name>.npy; the inputs are seeded, so two builds can be compared "
+                         "output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the benchmark's extended measurements and checks, i.e. whatever the headline figure "
+                         "does not need (none at present: a plain run already only sets up, warms up, times the steps, "
+                         "and with N > 1 verifies the exchange that decides which path's figure is reported)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if check_world(args.gpus) == "launch":
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
 
@@ -350,6 +385,8 @@ def main():
                 print(json.dumps({"exchange_verified": False, "detail": vinfo}), flush=True)
             raise SystemExit("bench.py: the cross-rank exchange disagrees with the process-group all-reduce")
 
+    if args.dump_outputs and rank == 0:  # (the ranks' replicas are identical: verified above)
+        dump_outputs(args.dump_outputs, trainer)
     ms = elapsed / args.steps * 1e3
     samples = global_batch * args.steps
     value = samples / elapsed

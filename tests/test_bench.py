@@ -297,6 +297,33 @@ class _FakeVerifyTrainer:
         pass
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: the coefficients a caller of the timed path receives (the model's width,
+    fp64) as DIR/coefficients.npy; an output over the size cap is cut to the same seeded sample of
+    its entries in every run."""
+    import bench
+
+    tr = _FakeVerifyTrainer()
+    tr.run_rounds(3)
+    out = tmp_path / "a" / "b"
+    assert bench.dump_outputs(str(out), tr) == {"coefficients": [6]}
+    got = np.load(out / "coefficients.npy")
+    assert got.dtype == np.float64
+    np.testing.assert_array_equal(got, np.arange(6) * 0.75)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 8)
+    bench.dump_outputs(str(out), tr)
+    first = np.load(out / "coefficients.npy")
+    bench.dump_outputs(str(tmp_path / "c"), tr)
+    np.testing.assert_array_equal(first, np.load(tmp_path / "c" / "coefficients.npy"))
+    assert first.shape == (4,) and set(first) <= set(np.arange(6) * 0.75) and np.all(np.diff(first) > 0)
+
+
+def test_bench_accepts_full_and_dump_outputs():
+    r = _bench_cmd("--gpus", "1", "--dry-run", "--full", "--dump-outputs", "unused")
+    assert r.returncode == 0, r.stderr
+    assert json.loads(r.stdout.splitlines()[-1])["world"] == 1
+
+
 def _verify_worker(rank, world, inject):
     import os
 
