@@ -17,7 +17,6 @@ Outputs: the input rows + ``predictionCol`` (int), and the merge table
 """
 from __future__ import annotations
 
-import ctypes
 from typing import List, Optional
 
 import numpy as np
@@ -34,15 +33,6 @@ from ..table import SparseColumn, Table
 
 LINKAGE_WARD, LINKAGE_COMPLETE, LINKAGE_SINGLE, LINKAGE_AVERAGE = "ward", "complete", "single", "average"
 _LINKAGE_CODE = {LINKAGE_WARD: 0, LINKAGE_COMPLETE: 1, LINKAGE_AVERAGE: 2, LINKAGE_SINGLE: 3}
-
-native.register_host_sigs({"fmlx_nnchain": ([ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
-                                             ctypes.c_int64)})
-
-
-native.register_kernel_sigs({"fmlx_pairwise_euclid_f64": [ctypes.c_void_p, ctypes.c_long, ctypes.c_int,
-                                                             ctypes.c_long, ctypes.c_void_p, ctypes.c_long,
-                                                             ctypes.c_int, ctypes.c_void_p]})
 
 
 def _euclid_device(X: torch.Tensor, condensed: bool) -> torch.Tensor:

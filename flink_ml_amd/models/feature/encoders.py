@@ -804,10 +804,6 @@ def _is_missing(x: torch.Tensor, missing: float) -> torch.Tensor:
     return torch.isnan(x) if math.isnan(missing) else (x == missing)
 
 
-native.register_kernel_sigs({"fmlx_masked_sum_f64": [native.c_void_p, native.c_long, native.c_double, native.c_int,
-                                                      native.c_void_p, native.c_void_p, native.c_void_p]})
-
-
 def _valid_sum_count(x: torch.Tensor, missing: float):
     """[sum, count] of a device column's entries that are neither NaN nor ``missing`` — one pass
     of csrc/colstats.hip masked_sum_kernel (no filtered copy of the column)."""

@@ -130,20 +130,6 @@ def _dict_col(t: Table, col: str):
     return None
 
 
-def _register_textops():
-    import ctypes
-
-    from ...ops import native
-
-    vp, i64 = ctypes.c_void_p, ctypes.c_int64
-    native.register_host_sigs({"fmlx_tokenize_ws_lower": ([vp, vp, i64, vp, vp, i64, vp, vp, vp], i64),
-                               "fmlx_tokenize_class": ([vp, vp, i64, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                        vp, vp, i64, vp, vp, vp], i64)})
-
-
-_register_textops()
-
-
 def simple_class_pattern(pattern: str):
     """(delimiter table over ASCII [128] uint8, plus) when ``pattern`` is ONE character atom (a
     literal, an escape, ``.``, a ``[...]`` class, ``\\s``/``\\d``/``\\w``) optionally followed by
@@ -300,11 +286,6 @@ def _per_string_arrays(t: Table, col: str, fn, native_kind: str = "", batched=No
 
 
 TF_ROWS_MAX_LEN = 32  # longest document the per-row device count takes (csrc/hash.hip fmlx_tf_rows)
-native.register_kernel_sigs({
-    "fmlx_tf_rows": [native.c_void_p, native.c_void_p, native.c_int, native.c_long, native.c_int, native.c_int,
-                     native.c_void_p, native.c_void_p, native.c_void_p, native.c_void_p, native.c_void_p, native.c_int,
-                     native.c_void_p],
-})
 
 
 def _tf_rows(off: torch.Tensor, idx: torch.Tensor, n: int, maxlen: int, binary: bool, nf: int):
@@ -393,11 +374,6 @@ class RegexTokenizer(Transformer, HasInputCol, HasOutputCol):
 
 
 NGRAM_DENSE_MAX = 1 << 26  # possible grams (V^n) up to which NGram uses the presence-table kernels
-native.register_kernel_sigs({
-    "fmlx_ngram_codes": [native.c_void_p, native.c_void_p, native.c_long, native.c_int, native.c_long, native.c_int,
-                         native.c_void_p, native.c_void_p, native.c_void_p, native.c_void_p, native.c_void_p,
-                         native.c_void_p],
-})
 
 
 def _ngram_device(dc, n: int, V: int) -> StringArrayColumn:
@@ -606,10 +582,6 @@ class HashingTF(Transformer, HasInputCol, HasOutputCol, HasNumFeatures):
 
 # ------------------------------------------------------------------------------------ FeatureHasher
 FH_ROWS_MAX_COLS = 16  # input columns the per-row device assembly takes (csrc/hash.hip fmlx_fh_rows)
-native.register_kernel_sigs({
-    "fmlx_fh_rows": [native.c_void_p, native.c_int, native.c_long, native.c_int, native.c_void_p, native.c_void_p,
-                     native.c_void_p, native.c_void_p, native.c_void_p],
-})
 
 
 @rw.register_stage
@@ -811,10 +783,6 @@ class CountVectorizerModel(ModelWithData, CountVectorizerModelParams):
 DF_BITMAP_MAX = 1 << 32
 DF_SEGMENTED_SORT = True
 CV_TFDF_MAX_V = 4096  # dictionary sizes the one-pass tf / df kernel takes (csrc/hash.hip cv_tfdf_kernel)
-native.register_kernel_sigs({
-    "fmlx_cv_tfdf": [native.c_void_p, native.c_void_p, native.c_long, native.c_int, native.c_void_p, native.c_void_p,
-                     native.c_void_p, native.c_void_p],
-})
 
 
 def _cv_counts_device(dc, tab, V: int, N: int):

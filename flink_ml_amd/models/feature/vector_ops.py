@@ -75,11 +75,6 @@ def _no_nan_device(x: torch.Tensor) -> bool:
 
 
 # ------------------------------------------------------------------------------------ Bucketizer
-native.register_kernel_sigs({"fmlx_bucketize": [native.c_void_p, native.c_long, native.c_void_p, native.c_int,
-                                                 native.c_int, native.c_void_p, native.c_void_p, native.c_void_p,
-                                                 native.c_void_p]})
-
-
 def _bucketize_device(x: torch.Tensor, s: torch.Tensor, keep: bool, want_mask: bool):
     """(bucket index f64, invalid mask u8 or None when every value is valid) of a device column in
     one kernel pass (csrc/colstats.hip bucketize_kernel)."""

@@ -11,8 +11,6 @@ Empty clusters become NaN centroids exactly like ``BLAS.scal(1/0)`` in the refer
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
@@ -31,9 +29,6 @@ from ..table import SparseColumn, Table
 from ..utils import graphs, tracing
 from .base import ModelWithData
 from .linear import rw_update
-
-native.register_host_sigs({"fmlx_reservoir_sample": ([ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-                                                      ctypes.c_void_p], ctypes.c_int)})
 
 
 def reservoir_sample_indices(n: int, k: int, seed: int) -> np.ndarray:

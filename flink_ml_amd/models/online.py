@@ -36,7 +36,6 @@ from ..linalg.vectors import DenseVector
 from ..ops import glm as gk
 from ..ops import kmeans as kk
 from ..ops import native
-from ..ops.native import c_double, c_int, c_long, c_void_p
 from ..param.param import FloatParam, IntParam, ParamValidators, StringParam
 from ..parallel import comm
 from ..stream import InMemorySource, StreamTable
@@ -46,18 +45,6 @@ from ..utils.tracing import MetricGroup
 from .base import ModelWithData
 from .kmeans import KMeansModel, _decode_kmeans, _encode_kmeans
 from .linear import LogisticRegressionModel, rw_update
-
-native.register_kernel_sigs({
-    "fmlx_ftrl_update": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_double, c_double,
-                         c_double, c_double, c_void_p],
-    "fmlx_ftrl_update2": [c_int, c_void_p, c_void_p, c_long, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                          c_long, c_double, c_double, c_double, c_double, c_void_p],
-    "fmlx_ftrl_grad_csr": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long,
-                           c_void_p, c_void_p],
-    "fmlx_okm_local_update": [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p, c_void_p],
-    "fmlx_okm_merge": [c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                       c_void_p, c_void_p],
-})
 
 
 def _as_stream(inp, batch_rows: Optional[int] = None) -> Iterable[Table]:

@@ -30,28 +30,6 @@ import torch
 
 from ..table import SparseColumn
 from . import native
-from .native import c_double, c_int, c_long, c_void_p
-
-native.register_kernel_sigs({
-    "fmlx_blas_rowreduce": [c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_double,
-                            c_void_p, c_void_p],
-    "fmlx_blas_normalize": [c_int, c_int, c_void_p, c_long, c_long, c_int, c_double, c_int, c_void_p, c_long, c_void_p],
-    "fmlx_blas_axpby": [c_int, c_void_p, c_long, c_void_p, c_long, c_long, c_int, c_double, c_void_p, c_double,
-                        c_void_p, c_void_p],
-    "fmlx_blas_hdot": [c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_void_p, c_long, c_void_p],
-    "fmlx_blas_gemv_t_blocks": ([c_long], c_long),
-    "fmlx_blas_gemv_t": [c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_void_p, c_void_p, c_double, c_void_p],
-    "fmlx_blas_csr_rowreduce": [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_double,
-                                c_void_p, c_void_p],
-    "fmlx_blas_csr_scale": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p],
-    "fmlx_blas_csr_axpy_dense": [c_int, c_void_p, c_void_p, c_void_p, c_double, c_long, c_int, c_void_p, c_long,
-                                 c_void_p],
-    "fmlx_blas_csr_csr_dot": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p,
-                              c_void_p],
-    "fmlx_blas_gather_cols": [c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_void_p, c_void_p],
-    "fmlx_blas_gather_prod": [c_int, c_void_p, c_long, c_int, c_void_p, c_int, c_long, c_int, c_void_p, c_void_p],
-    "fmlx_blas_interaction": [c_int, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p],
-})
 
 OP_DOT, OP_DOTV, OP_NORM2, OP_NORM1, OP_NORMINF, OP_NORMP, OP_ASUM = range(7)
 
@@ -356,8 +334,9 @@ def interaction(mats: Sequence[torch.Tensor]) -> torch.Tensor:
         ptrs = (ctypes.c_void_p * len(mats))(*[m.data_ptr() for m in mats])
         lds = (ctypes.c_long * len(mats))(*[m.stride(0) for m in mats])
         dims = (ctypes.c_long * len(mats))(*[m.shape[1] for m in mats])
-        native.call("fmlx_blas_interaction", len(mats), ctypes.cast(ptrs, c_void_p), ctypes.cast(lds, c_void_p),
-                    ctypes.cast(dims, c_void_p), n, native.ptr(out), native.stream_ptr(out.device))
+        native.call("fmlx_blas_interaction", len(mats), ctypes.cast(ptrs, ctypes.c_void_p),
+                    ctypes.cast(lds, ctypes.c_void_p), ctypes.cast(dims, ctypes.c_void_p), n, native.ptr(out),
+                    native.stream_ptr(out.device))
         return out
     out = mats[0]
     for m in mats[1:]:

@@ -11,6 +11,10 @@ which objects the last build compiled vs reused. ``FMLX_FORCE_BUILD=1`` (or ``--
 recompiles everything. At load time ``native`` compares the manifest's source digest with the
 tree and refuses a library built from other sources (a stale binary shipped with the tree).
 
+The manifest also carries each library's ``api``: the ctypes signature of every entry point,
+parsed from the C definitions marked ``FMLX_API`` (``api_signatures``). ``native`` binds the
+libraries' functions from it, so the C prototypes are the only description of the ABI.
+
 ``--sanitize``: the host runtime rebuilt with ``-fsanitize=address,undefined`` into
 ``_lib/libfmlx_host_asan.so`` (the CPU test-suite runs the host paths against it, see
 ``tests/test_native_build.py``); GPU code is never built with sanitizers.
@@ -25,6 +29,7 @@ import glob
 import hashlib
 import json
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -67,6 +72,73 @@ def source_digest(which: str) -> str:
     """sha256 over the (relative name, content hash) of every source of a library."""
     srcs, hdrs = kernel_sources() if which == "kernels" else host_sources()
     return _digest([(os.path.relpath(f, CSRC), _sha(f)) for f in srcs + hdrs])
+
+
+# The ctypes signature of every entry point is derived from its C definition: a function is an
+# entry point iff its definition carries API_MARKER (csrc/common.h, csrc/host/api.h), and these are
+# all the parameter / return types one may use (values: attribute names of ``ctypes``). Every
+# pointer is a c_void_p (takes an address, None, bytes or a ctypes array); ``void`` returns None.
+API_MARKER = "FMLX_API"
+C_TYPES = {
+    "int": "c_int", "int32_t": "c_int",
+    "unsigned": "c_uint", "unsigned int": "c_uint", "uint32_t": "c_uint",
+    "long": "c_int64", "long long": "c_int64", "int64_t": "c_int64",
+    "unsigned long": "c_uint64", "unsigned long long": "c_uint64", "uint64_t": "c_uint64", "size_t": "c_uint64",
+    "float": "c_float",
+    "double": "c_double",
+}
+_TYPE_WORDS = {"void", "char", "short", "int", "long", "signed", "unsigned", "float", "double", "bool"}
+# string and character literals (matched so that a "//" inside one opens no comment), comments
+_NOT_CODE = re.compile(r'"(?:\\.|[^"\\\n])*"|\'(?:\\.|[^\'\\\n])*\'|//[^\n]*|/\*.*?\*/', re.S)
+_MARKED = re.compile(r"%s\b([^(){};]*?)(\w+)\s*\(" % API_MARKER)  # marker, return type, name, "("
+
+
+def _c_type(decl: str, named: bool, what: str):
+    """ctypes name of one C parameter declaration (``named``: may end in the parameter's name) or
+    return type; raises for anything that is not in C_TYPES: never a guess."""
+    if not re.search(r"[^\w\s*]", decl):
+        if "*" in decl:
+            return "c_void_p"
+        words = [w for w in decl.split() if w not in ("const", "__restrict__")]
+        if not named and words == ["void"]:
+            return None
+        if named and len(words) > 1 and words[-1] not in _TYPE_WORDS and " ".join(words) not in C_TYPES:
+            words.pop()  # the parameter's name
+        if " ".join(words) in C_TYPES:
+            return C_TYPES[" ".join(words)]
+    raise ValueError("%s: C type '%s' has no ctypes mapping (ops/build.py C_TYPES)" % (what, " ".join(decl.split())))
+
+
+def parse_api(text: str, where: str, api: dict = None) -> dict:
+    """Adds ``{name: (restype, [argtype, ...])}`` of every API_MARKER function in the C/HIP source
+    ``text`` (``where``: its file name, for error messages) to ``api`` and returns it."""
+    api = {} if api is None else api
+    text = _NOT_CODE.sub(" ", text)
+    for marker in re.finditer(r"\b%s\b" % API_MARKER, text):
+        m = _MARKED.match(text, marker.start())
+        if m is None:
+            raise ValueError("%s: %s is not followed by 'type name(parameters)'" % (where, API_MARKER))
+        name, what = m.group(2), "%s in %s" % (m.group(2), where)
+        end = text.find(")", m.end())
+        params = text[m.end():end]
+        if end < 0 or "(" in params:
+            raise ValueError("%s: cannot read the parameter list" % what)
+        if name in api:
+            raise ValueError("%s: entry point defined twice" % what)
+        plist = [] if params.strip() in ("", "void") else params.split(",")
+        api[name] = (_c_type(m.group(1), False, what), [_c_type(p, True, what) for p in plist])
+    return api
+
+
+def api_signatures(which: str) -> dict:
+    """``{name: (restype, [argtype, ...])}`` (ctypes attribute names; restype None: void) of every
+    entry point of the library ``which`` ("kernels" / "host"), parsed from its sources."""
+    srcs, _ = kernel_sources() if which == "kernels" else host_sources()
+    api = {}
+    for path in srcs:
+        with open(path) as f:
+            parse_api(f.read(), os.path.relpath(path, CSRC), api)
+    return api
 
 
 def _load_manifest() -> dict:
@@ -165,7 +237,8 @@ def build_kernels(force: bool = False, jobs: int = 8, verbose: bool = False) -> 
     if relink:
         _run([hipcc, "--offload-arch=%s" % ARCH, "-shared", "-fPIC", "-o", KERNEL_LIB] + objs)
     man = _load_manifest()
-    man["kernels"] = {"objects": keys, "source_digest": digest, "arch": ARCH, "compiler": ver.splitlines()[0] if ver else "?",
+    man["kernels"] = {"objects": keys, "source_digest": digest, "api": api_signatures("kernels"), "arch": ARCH,
+                      "compiler": ver.splitlines()[0] if ver else "?",
                       "compiled": sorted(os.path.basename(s) for s, _ in todo),
                       "reused": sorted(n for n in keys if n not in {os.path.basename(s) for s, _ in todo}),
                       "linked": relink, "forced": force, "time": time.strftime("%Y-%m-%dT%H:%M:%S")}
@@ -195,8 +268,8 @@ def build_host(force: bool = False, verbose: bool = False, sanitize: bool = Fals
         print("[g++] host runtime%s (%d files)" % (" (ASan+UBSan)" if sanitize else "", len(srcs)), flush=True)
     _run([cxx] + flags + ["-o", target] + srcs + ["-lpthread"])
     man = _load_manifest()
-    man[section] = {"key": key, "source_digest": digest, "compiled": True, "flags": flags,
-                    "time": time.strftime("%Y-%m-%dT%H:%M:%S")}
+    man[section] = {"key": key, "source_digest": digest, "api": api_signatures("host"), "compiled": True,
+                    "flags": flags, "time": time.strftime("%Y-%m-%dT%H:%M:%S")}
     _save_manifest(man)
     return target
 
@@ -207,18 +280,21 @@ def build_all(force: bool = False, jobs: int = 8, verbose: bool = False):
     return k, h
 
 
-def check_fresh(which: str) -> None:
+def check_fresh(which: str):
     """Raises if the library ``which`` ("kernels" / "host") was built from other sources than the
-    tree holds (sources present but digest differs), i.e. a stale prebuilt binary."""
+    tree holds (sources present but digest differs), i.e. a stale prebuilt binary. Returns the
+    accepted manifest record's table of entry points (api_signatures at build time), or None when
+    there is no such record."""
     srcs, _ = kernel_sources() if which == "kernels" else host_sources()
     if not srcs or os.environ.get("FMLX_SKIP_FRESHNESS", "0") == "1":
-        return
+        return None
     rec = _load_manifest().get(which, {})
     if not rec:
-        return  # library built by hand / older tree: nothing to compare against
+        return None  # library built by hand / older tree: nothing to compare against
     if rec.get("source_digest") != source_digest(which):
         raise RuntimeError("native %s library is stale: built from other sources than this tree "
                            "(run python -m flink_ml_amd.ops.build)" % which)
+    return rec.get("api")
 
 
 def main(argv=None):

@@ -15,21 +15,6 @@ import numpy as np
 import torch
 
 from . import native, sorting
-from .native import c_int, c_long, c_void_p
-
-native.register_kernel_sigs({
-    "fmlx_cs_tile": [],
-    "fmlx_cs_lds_ints": [],
-    "fmlx_cs_flags": [c_int, c_void_p, c_long, c_long, c_int, c_void_p, c_void_p, c_void_p],
-    "fmlx_cs_ihist": [c_int, c_void_p, c_long, c_long, c_int, c_long, c_int, c_void_p, c_void_p],
-    "fmlx_cs_hist": [c_int, c_void_p, c_long, c_long, c_int, c_void_p, c_int, c_long, c_int, c_void_p, c_void_p],
-    "fmlx_cs_col_keys": [c_int, c_void_p, c_long, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "fmlx_cs_distinct": [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p, c_void_p,
-                         c_void_p, c_void_p],
-    "fmlx_cs_chist": [c_void_p, c_long, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
-    "fmlx_cs_small_distinct": [c_void_p, c_long, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                               c_void_p],
-})
 
 # integer tables up to this many cells are counted directly (value range × labels × features)
 MAX_TABLE = 1 << 27
@@ -63,9 +48,6 @@ def flags(X: torch.Tensor) -> Tuple[float, float, bool]:
     return mn, mx, non != 0.0
 
 
-native.register_kernel_sigs({
-    "fmlx_cv_tfdf": [c_void_p, c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-})
 CODE_COUNTS_MAX_V = 4096  # dictionary sizes of the one-pass count kernel (csrc/hash.hip cv_tfdf_kernel)
 CODE_COUNTS_SEG = 4096  # codes per pseudo-document (the kernel's unit of work per wave)
 

@@ -35,7 +35,9 @@
 #include "xgmi.h"
 #include "glm_core.h"
 
-FMLX_API void fmlx_glm_sparse_set_trace(void* trace);  // glm_sparse.hip
+// defined (and exported) in glm_sparse.hip; a declaration carries no FMLX_API: the marker stands on
+// definitions only, one per entry point
+extern "C" void fmlx_glm_sparse_set_trace(void* trace);
 
 namespace {
 
@@ -1403,8 +1405,10 @@ int launch_pred_cpl(int cpl, const void* X, long ld, long n, int d, const void* 
 
 #ifdef FMLX_ISA_PROBE
 // ISA inspection builds (hipcc --offload-device-only -S -DFMLX_ISA_PROBE): only the flagship round
-// kernel's variants are instantiated, so the .s comes out in seconds, not minutes
-FMLX_API int fmlx_glm_isa_probe(int u, const void* X, long ld, const void* y, void* coef, int* state, const GlmTail* tl) {
+// kernel's variants are instantiated, so the .s comes out in seconds, not minutes (no FMLX_API: the
+// library never holds this function, so it is not one of its entry points)
+extern "C" int fmlx_glm_isa_probe(int u, const void* X, long ld, const void* y, void* coef, int* state,
+                                  const GlmTail* tl) {
   return launch_grad<bf16_t, 8, 2>(u, X, ld, y, nullptr, coef, 1, 1000, 1, 0, state, nullptr, 224, *tl, 1, 0);
 }
 #else

@@ -21,6 +21,8 @@
 #include <string>
 #include <vector>
 
+#include "api.h"
+
 namespace {
 struct Segment {
   char* mem = nullptr;    // non-null while memory-resident
@@ -116,9 +118,7 @@ int new_segment(Cache* c, int64_t need) {
 }
 }  // namespace
 
-extern "C" {
-
-void* fmlx_dc_open(const char* dir, int64_t seg_bytes, int64_t mem_budget) {
+FMLX_API void* fmlx_dc_open(const char* dir, int64_t seg_bytes, int64_t mem_budget) {
   ::mkdir(dir, 0755);
   Cache* c = new Cache();
   c->dir = dir;
@@ -128,7 +128,7 @@ void* fmlx_dc_open(const char* dir, int64_t seg_bytes, int64_t mem_budget) {
 }
 
 // Appends one record; returns its index (>= 0) or a negative error.
-int64_t fmlx_dc_append(void* h, const void* data, int64_t n) {
+FMLX_API int64_t fmlx_dc_append(void* h, const void* data, int64_t n) {
   Cache* c = (Cache*)h;
   std::lock_guard<std::mutex> g(c->mu);
   int idx = (int)c->segs.size() - 1;
@@ -153,15 +153,15 @@ int64_t fmlx_dc_append(void* h, const void* data, int64_t n) {
   return (int64_t)c->recs.size() - 1;
 }
 
-int64_t fmlx_dc_num_records(void* h) { return (int64_t)((Cache*)h)->recs.size(); }
+FMLX_API int64_t fmlx_dc_num_records(void* h) { return (int64_t)((Cache*)h)->recs.size(); }
 
-int64_t fmlx_dc_record_size(void* h, int64_t i) {
+FMLX_API int64_t fmlx_dc_record_size(void* h, int64_t i) {
   Cache* c = (Cache*)h;
   return (i < 0 || i >= (int64_t)c->recs.size()) ? -1 : c->recs[i].len;
 }
 
 // Copies record i into dst (capacity >= its size). Returns 0 or a negative error.
-int fmlx_dc_read(void* h, int64_t i, void* dst) {
+FMLX_API int fmlx_dc_read(void* h, int64_t i, void* dst) {
   Cache* c = (Cache*)h;
   if (i < 0 || i >= (int64_t)c->recs.size()) return -1;
   const Rec r = c->recs[i];
@@ -175,7 +175,7 @@ int fmlx_dc_read(void* h, int64_t i, void* dst) {
 
 // Spills every memory segment to disk (returns 0 or a negative error).
 // address of record i inside a memory segment (nullptr: the record lives in a file segment)
-void* fmlx_dc_record_ptr(void* h, int64_t i) {
+FMLX_API void* fmlx_dc_record_ptr(void* h, int64_t i) {
   Cache* c = (Cache*)h;
   if (i < 0 || i >= (int64_t)c->recs.size()) return nullptr;
   const Rec r = c->recs[i];
@@ -184,7 +184,7 @@ void* fmlx_dc_record_ptr(void* h, int64_t i) {
 }
 
 // memory segment idx: its base and capacity (0 / nullptr for file segments or a bad index)
-void* fmlx_dc_segment_mem(void* h, int64_t idx, int64_t* cap) {
+FMLX_API void* fmlx_dc_segment_mem(void* h, int64_t idx, int64_t* cap) {
   Cache* c = (Cache*)h;
   *cap = 0;
   if (idx < 0 || idx >= (int64_t)c->segs.size() || !c->segs[idx].mem) return nullptr;
@@ -192,7 +192,7 @@ void* fmlx_dc_segment_mem(void* h, int64_t idx, int64_t* cap) {
   return c->segs[idx].mem;
 }
 
-int fmlx_dc_spill_all(void* h) {
+FMLX_API int fmlx_dc_spill_all(void* h) {
   Cache* c = (Cache*)h;
   std::lock_guard<std::mutex> g(c->mu);
   for (int i = 0; i < (int)c->segs.size(); ++i) {
@@ -203,7 +203,7 @@ int fmlx_dc_spill_all(void* h) {
 }
 
 // stats[0..3] = memory bytes, file bytes, #segments, #memory segments
-void fmlx_dc_stats(void* h, int64_t* stats) {
+FMLX_API void fmlx_dc_stats(void* h, int64_t* stats) {
   Cache* c = (Cache*)h;
   int64_t m = 0;
   for (auto& s : c->segs) m += s.mem ? 1 : 0;
@@ -216,7 +216,7 @@ void fmlx_dc_stats(void* h, int64_t* stats) {
 // Spills everything and writes `<dir>/MANIFEST` (binary: int64 nsegs, per segment int64 used;
 // int64 nrecs, per record int32 seg + int64 off + int64 len). Afterwards the cache can be
 // reopened with fmlx_dc_reopen (checkpoint/restore of cached inputs).
-int fmlx_dc_finish(void* h) {
+FMLX_API int fmlx_dc_finish(void* h) {
   Cache* c = (Cache*)h;
   int rc = fmlx_dc_spill_all(h);
   if (rc) return rc;
@@ -238,7 +238,7 @@ int fmlx_dc_finish(void* h) {
   return std::rename(tmp.c_str(), fin.c_str()) == 0 ? 0 : -4;
 }
 
-void* fmlx_dc_reopen(const char* dir) {
+FMLX_API void* fmlx_dc_reopen(const char* dir) {
   const std::string man = std::string(dir) + "/MANIFEST";
   FILE* f = std::fopen(man.c_str(), "rb");
   if (!f) return nullptr;
@@ -274,7 +274,7 @@ void* fmlx_dc_reopen(const char* dir) {
 }
 
 // Frees memory, closes files; deletes the segment files and manifest when `remove` is set.
-void fmlx_dc_close(void* h, int remove) {
+FMLX_API void fmlx_dc_close(void* h, int remove) {
   Cache* c = (Cache*)h;
   for (auto& s : c->segs) {
     if (s.mem) std::free(s.mem);
@@ -286,5 +286,4 @@ void fmlx_dc_close(void* h, int remove) {
     ::rmdir(c->dir.c_str());
   }
   delete c;
-}
 }

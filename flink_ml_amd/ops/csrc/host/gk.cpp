@@ -6,11 +6,11 @@
 #include <cmath>
 #include <cstdint>
 
-extern "C" {
+#include "api.h"
 
 // Merge the sorted head buffer `h` into the samples; returns the new sample count (ns + nh).
-int64_t fmlx_gk_insert(const double* sv, const int64_t* sg, const int64_t* sd, int64_t ns, const double* h,
-                       int64_t nh, int64_t delta_base, double* ov, int64_t* og, int64_t* od) {
+FMLX_API int64_t fmlx_gk_insert(const double* sv, const int64_t* sg, const int64_t* sd, int64_t ns, const double* h,
+                                int64_t nh, int64_t delta_base, double* ov, int64_t* og, int64_t* od) {
   int64_t o = 0, cur = 0;
   for (int64_t i = 0; i < nh; ++i) {
     while (cur < ns && sv[cur] <= h[i]) {
@@ -37,8 +37,8 @@ int64_t fmlx_gk_insert(const double* sv, const int64_t* sg, const int64_t* sd, i
 
 // Backward compression with merge threshold `thr`; writes the result front-aligned and returns
 // its length. Output arrays may not alias the input.
-int64_t fmlx_gk_compress(const double* v, const int64_t* g, const int64_t* d, int64_t n, double thr, double* ov,
-                         int64_t* og, int64_t* od) {
+FMLX_API int64_t fmlx_gk_compress(const double* v, const int64_t* g, const int64_t* d, int64_t n, double thr,
+                                  double* ov, int64_t* og, int64_t* od) {
   if (n == 0) return 0;
   // build back to front into the tail of the output, then shift to the front
   int64_t w = n;  // next free slot (exclusive) from the back
@@ -78,9 +78,9 @@ int64_t fmlx_gk_compress(const double* v, const int64_t* g, const int64_t* d, in
 
 // Ordered merge of two summaries (before compression). add_a is added to a sample of `a` once
 // any sample of `b` precedes it, and vice versa; the leftover tail is copied unchanged.
-int64_t fmlx_gk_merge(const double* av, const int64_t* ag, const int64_t* ad, int64_t na, const double* bv,
-                      const int64_t* bg, const int64_t* bd, int64_t nb, int64_t add_a, int64_t add_b, double* ov,
-                      int64_t* og, int64_t* od) {
+FMLX_API int64_t fmlx_gk_merge(const double* av, const int64_t* ag, const int64_t* ad, int64_t na, const double* bv,
+                               const int64_t* bg, const int64_t* bd, int64_t nb, int64_t add_a, int64_t add_b,
+                               double* ov, int64_t* og, int64_t* od) {
   int64_t i = 0, j = 0, o = 0;
   while (i < na && j < nb) {
     if (av[i] < bv[j]) {
@@ -110,8 +110,8 @@ int64_t fmlx_gk_merge(const double* av, const int64_t* ag, const int64_t* ad, in
 }
 
 // Answers sorted percentiles `ps` (ascending) into `out` in the same order.
-void fmlx_gk_query(const double* v, const int64_t* g, const int64_t* d, int64_t n, int64_t count, double rel_err,
-                   const double* ps, int64_t np, double* out) {
+FMLX_API void fmlx_gk_query(const double* v, const int64_t* g, const int64_t* d, int64_t n, int64_t count,
+                            double rel_err, const double* ps, int64_t np, double* out) {
   double target = (double)INT64_MIN;
   for (int64_t i = 0; i < n; ++i) target = std::fmax(target, (double)(d[i] + g[i]));
   target /= 2;
@@ -146,5 +146,4 @@ void fmlx_gk_query(const double* v, const int64_t* g, const int64_t* d, int64_t 
       }
     }
   }
-}
 }

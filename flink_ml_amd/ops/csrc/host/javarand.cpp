@@ -5,6 +5,8 @@
 #include <cmath>
 #include <cstdint>
 
+#include "api.h"
+
 namespace {
 struct JRandom {
   uint64_t seed;
@@ -42,11 +44,9 @@ struct JRandom {
 };
 }  // namespace
 
-extern "C" {
-
 // Reservoir sample of k positions out of n (SamplingOperator.processElement semantics).
 // Writes the chosen positions (in reservoir slot order) to out[0..min(n,k)); returns that count.
-int fmlx_reservoir_sample(int64_t n, int32_t k, int64_t seed, int64_t* out) {
+FMLX_API int fmlx_reservoir_sample(int64_t n, int32_t k, int64_t seed, int64_t* out) {
   JRandom rnd(seed);
   int64_t filled = 0;
   for (int64_t i = 0; i < n; ++i) {
@@ -69,8 +69,8 @@ int fmlx_reservoir_sample(int64_t n, int32_t k, int64_t seed, int64_t* out) {
 // not a power of two and u − u % b + b − 1 ≥ 2^31. Writes the rejected positions (ascending) to
 // rej and returns their count; *done receives 1 if the scan proved that draw n − 1 happens before
 // position `npos` (the generated stream was long enough), else 0.
-int64_t fmlx_reservoir_rejections(int64_t n, int32_t k, int64_t npos, const int32_t* cand_p, const int32_t* cand_u,
-                                  int64_t ncand, int64_t* rej, int32_t* done) {
+FMLX_API int64_t fmlx_reservoir_rejections(int64_t n, int32_t k, int64_t npos, const int32_t* cand_p,
+                                           const int32_t* cand_u, int64_t ncand, int64_t* rej, int32_t* done) {
   // The decision for a candidate depends on R through its bound; the dependency chain through
   // R would put a division on every step's critical path. Instead the next candidate's decision is
   // computed for both values R can take there (R, R + 1) while this one's is resolved — two
@@ -99,24 +99,23 @@ int64_t fmlx_reservoir_rejections(int64_t n, int32_t k, int64_t npos, const int3
   return R;
 }
 
-void fmlx_java_next31(int64_t seed, int64_t start, int64_t n, int32_t* out) {
+FMLX_API void fmlx_java_next31(int64_t seed, int64_t start, int64_t n, int32_t* out) {
   JRandom rnd(seed);
   for (int64_t i = 0; i < start; ++i) rnd.next(31);
   for (int64_t i = 0; i < n; ++i) out[i] = rnd.next(31);
 }
 
-void fmlx_java_next_doubles(int64_t seed, int64_t n, double* out) {
+FMLX_API void fmlx_java_next_doubles(int64_t seed, int64_t n, double* out) {
   JRandom rnd(seed);
   for (int64_t i = 0; i < n; ++i) out[i] = rnd.next_double();
 }
 
-void fmlx_java_next_gaussians(int64_t seed, int64_t n, double* out) {
+FMLX_API void fmlx_java_next_gaussians(int64_t seed, int64_t n, double* out) {
   JRandom rnd(seed);
   for (int64_t i = 0; i < n; ++i) out[i] = rnd.next_gaussian();
 }
 
-void fmlx_java_next_ints(int64_t seed, int64_t n, int32_t bound, int32_t* out) {
+FMLX_API void fmlx_java_next_ints(int64_t seed, int64_t n, int32_t bound, int32_t* out) {
   JRandom rnd(seed);
   for (int64_t i = 0; i < n; ++i) out[i] = rnd.next_int(bound);
-}
 }

@@ -14,6 +14,8 @@
 #include <thread>
 #include <vector>
 
+#include "api.h"
+
 namespace {
 inline uint32_t rotl(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
 inline uint32_t mix_k1(uint32_t k1) { return rotl(k1 * 0xcc9e2d51u, 15) * 0x1b873593u; }
@@ -117,11 +119,9 @@ void parallel_for(int64_t n, int nthreads, F f) {
 }
 }  // namespace
 
-extern "C" {
-
 // out_hash[i] = murmur3_32(prefix ++ Double.toString(vals[i])) (UTF-16 semantics)
-void fmlx_hash_prefixed_doubles(const uint16_t* prefix, int32_t plen, const double* vals, int64_t n, int32_t* out_hash,
-                                int32_t nthreads) {
+FMLX_API void fmlx_hash_prefixed_doubles(const uint16_t* prefix, int32_t plen, const double* vals, int64_t n,
+                                         int32_t* out_hash, int32_t nthreads) {
   parallel_for(n, nthreads, [&](int64_t s, int64_t e) {
     char buf[64];
     for (int64_t i = s; i < e; ++i) {
@@ -133,11 +133,10 @@ void fmlx_hash_prefixed_doubles(const uint16_t* prefix, int32_t plen, const doub
 
 // Double.toString for a batch: writes the strings back to back into `chars` (capacity 32 per
 // value) and their end offsets into `ends`.
-void fmlx_java_double_strings(const double* vals, int64_t n, char* chars, int64_t* ends) {
+FMLX_API void fmlx_java_double_strings(const double* vals, int64_t n, char* chars, int64_t* ends) {
   int64_t o = 0;
   for (int64_t i = 0; i < n; ++i) {
     o += java_double_string(vals[i], chars + o);
     ends[i] = o;
   }
-}
 }

@@ -4,6 +4,8 @@
 #include <cstdint>
 #include <cstring>
 
+#include "api.h"
+
 namespace {
 inline uint32_t rotl(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
 inline uint32_t mix_k1(uint32_t k1) {
@@ -38,20 +40,18 @@ inline int32_t hash_chars(const uint16_t* cs, int64_t len) {
 }
 }  // namespace
 
-extern "C" {
 // strings given as UTF-16 code units, string i = units[offsets[i] .. offsets[i+1])
-void fmlx_murmur3_chars(const uint16_t* units, const int64_t* offsets, int64_t n, int32_t* out) {
+FMLX_API void fmlx_murmur3_chars(const uint16_t* units, const int64_t* offsets, int64_t n, int32_t* out) {
   for (int64_t i = 0; i < n; ++i) out[i] = hash_chars(units + offsets[i], offsets[i + 1] - offsets[i]);
 }
-void fmlx_murmur3_ints(const int32_t* v, int64_t n, int32_t* out) {
+FMLX_API void fmlx_murmur3_ints(const int32_t* v, int64_t n, int32_t* out) {
   for (int64_t i = 0; i < n; ++i) out[i] = (int32_t)fmix(mix_h1(0, mix_k1((uint32_t)v[i])), 4);
 }
-void fmlx_murmur3_longs(const int64_t* v, int64_t n, int32_t* out) {
+FMLX_API void fmlx_murmur3_longs(const int64_t* v, int64_t n, int32_t* out) {
   for (int64_t i = 0; i < n; ++i) {
     const uint64_t x = (uint64_t)v[i];
     uint32_t h1 = mix_h1(0, mix_k1((uint32_t)x));
     h1 = mix_h1(h1, mix_k1((uint32_t)(x >> 32)));
     out[i] = (int32_t)fmix(h1, 8);
   }
-}
 }

@@ -16,6 +16,8 @@
 #include <limits>
 #include <vector>
 
+#include "api.h"
+
 namespace {
 
 struct LabelSet {
@@ -104,13 +106,11 @@ inline double lance_williams(double dik, double djk, double dij, double si, doub
 
 }  // namespace
 
-extern "C" {
-
 // pairwise: n*(n-1)/2 distances between the n points, row-major upper triangle (i < j).
 // Outputs n-1 merges (a, b, merged label, distance) in NN-chain discovery order and the
 // cluster sizes of all 2n-1 nodes. Returns the number of merges or -1 on bad input.
-int64_t fmlx_nnchain(const double* pairwise, int64_t n, int32_t linkage, int64_t* out_a, int64_t* out_b,
-                     int64_t* out_merged, double* out_dist, int64_t* sizes) {
+FMLX_API int64_t fmlx_nnchain(const double* pairwise, int64_t n, int32_t linkage, int64_t* out_a, int64_t* out_b,
+                              int64_t* out_merged, double* out_dist, int64_t* sizes) {
   if (n < 1) return -1;
   if (n == 1) {
     sizes[0] = 1;
@@ -174,5 +174,3 @@ int64_t fmlx_nnchain(const double* pairwise, int64_t n, int32_t linkage, int64_t
   }
   return m;
 }
-
-}  // extern "C"

@@ -19,6 +19,8 @@
 #include <thread>
 #include <vector>
 
+#include "api.h"
+
 namespace {
 
 inline uint64_t mix64(uint64_t h) {
@@ -70,9 +72,7 @@ void parallel_for(int64_t n, int64_t grain, F&& f) {
 
 }  // namespace
 
-extern "C" {
-
-void fmlx_str_hash64(const uint16_t* units, const int64_t* offs, int64_t n, uint64_t* out) {
+FMLX_API void fmlx_str_hash64(const uint16_t* units, const int64_t* offs, int64_t n, uint64_t* out) {
   parallel_for(n, 1 << 16, [&](int64_t a, int64_t b) {
     for (int64_t i = a; i < b; ++i) out[i] = hash_units(units + offs[i], offs[i + 1] - offs[i]);
   });
@@ -80,7 +80,8 @@ void fmlx_str_hash64(const uint16_t* units, const int64_t* offs, int64_t n, uint
 
 // perm = a stable ordering of [0, n) by String.compareTo (descending: reversed comparison, still
 // stable among equal strings). Chunks are sorted in parallel, then merged pairwise.
-void fmlx_str_argsort(const uint16_t* units, const int64_t* offs, int64_t n, int descending, int64_t* perm) {
+FMLX_API void fmlx_str_argsort(const uint16_t* units, const int64_t* offs, int64_t n, int descending,
+                               int64_t* perm) {
   std::iota(perm, perm + n, (int64_t)0);
   auto less = [&](int64_t x, int64_t y) {
     const uint16_t* a = units + offs[x];
@@ -110,8 +111,8 @@ void fmlx_str_argsort(const uint16_t* units, const int64_t* offs, int64_t n, int
 }
 
 // out[q] = index of the first dictionary string equal to query q, or −1
-void fmlx_str_lookup(const uint16_t* du, const int64_t* doffs, int64_t nd, const uint16_t* qu, const int64_t* qoffs,
-                     int64_t nq, int64_t* out) {
+FMLX_API void fmlx_str_lookup(const uint16_t* du, const int64_t* doffs, int64_t nd, const uint16_t* qu,
+                              const int64_t* qoffs, int64_t nq, int64_t* out) {
   int64_t cap = 16;
   while (cap < 2 * nd) cap <<= 1;
   std::vector<uint64_t> dh((size_t)nd);
@@ -153,8 +154,8 @@ void fmlx_str_lookup(const uint16_t* du, const int64_t* doffs, int64_t nd, const
 }
 
 // Gather strings idx[0..m) of a table into (out_units, out_offs); out_offs[m] = total units.
-void fmlx_str_gather(const uint16_t* units, const int64_t* offs, const int64_t* idx, int64_t m, uint16_t* out_units,
-                     int64_t* out_offs) {
+FMLX_API void fmlx_str_gather(const uint16_t* units, const int64_t* offs, const int64_t* idx, int64_t m,
+                              uint16_t* out_units, int64_t* out_offs) {
   out_offs[0] = 0;
   for (int64_t i = 0; i < m; ++i) out_offs[i + 1] = out_offs[i] + (offs[idx[i] + 1] - offs[idx[i]]);
   parallel_for(m, 1 << 16, [&](int64_t a, int64_t b) {
@@ -168,7 +169,7 @@ void fmlx_str_gather(const uint16_t* units, const int64_t* offs, const int64_t* 
 // Iteration order of a java.util.HashMap (table capacity `cap`, a power of two) filled with keys
 // of Java hashes h[0..n) in index order, no treeified bins: by bucket (h ^ h >>> 16) & (cap − 1),
 // insertion order inside a bucket (HashMap.java putVal / resize keep it) — a counting sort.
-void fmlx_hashmap_order(const int32_t* h, int64_t n, int64_t cap, int64_t* out) {
+FMLX_API void fmlx_hashmap_order(const int32_t* h, int64_t n, int64_t cap, int64_t* out) {
   std::vector<int64_t> start((size_t)cap + 1, 0);
   std::vector<uint32_t> b((size_t)n);
   for (int64_t i = 0; i < n; ++i) {
@@ -179,5 +180,3 @@ void fmlx_hashmap_order(const int32_t* h, int64_t n, int64_t cap, int64_t* out) 
   for (int64_t c = 0; c < cap; ++c) start[c + 1] += start[c];
   for (int64_t i = 0; i < n; ++i) out[start[b[i]]++] = i;
 }
-
-}  // extern "C"

@@ -10,6 +10,8 @@
 #include <cstring>
 #include <vector>
 
+#include "api.h"
+
 namespace {
 inline bool java_ws(unsigned char c) { return c == ' ' || c == '\t' || c == '\n' || c == 0x0B || c == '\f' || c == '\r'; }
 inline char lower_ascii(char c) { return (c >= 'A' && c <= 'Z') ? (char)(c + 32) : c; }
@@ -31,8 +33,6 @@ inline uint64_t hash_bytes(const char* p, int64_t len) {
 }
 }  // namespace
 
-extern "C" {
-
 // bytes/offs: n strings (offs[n+1]). Outputs: ntok[n] tokens per string, tok_ids[] (capacity
 // tok_cap) the vocabulary id of every token in order, vocab_bytes (capacity = total bytes +
 // tok_cap) the distinct tokens in first-seen order, each followed by '\n' (a token never contains
@@ -41,9 +41,9 @@ extern "C" {
 // General form: split on a single-character class (`delim`, a 128-entry table over ASCII), `plus`
 // = runs of delimiters are ONE delimiter (pattern `X+`), optional lowercasing, tokens shorter than
 // `min_len` dropped (RegexTokenizer.java:74-90 with gaps = true on a one-character pattern).
-int64_t fmlx_tokenize_class(const char* bytes, const int64_t* offs, int64_t n, const uint8_t* delim, int plus,
-                            int lower, int min_len, int32_t* ntok, int32_t* tok_ids, int64_t tok_cap,
-                            char* vocab_bytes, int64_t* vocab_offs, int64_t* nvocab) {
+FMLX_API int64_t fmlx_tokenize_class(const char* bytes, const int64_t* offs, int64_t n, const uint8_t* delim, int plus,
+                                     int lower, int min_len, int32_t* ntok, int32_t* tok_ids, int64_t tok_cap,
+                                     char* vocab_bytes, int64_t* vocab_offs, int64_t* nvocab) {
   auto isd = [&](unsigned char c) -> bool { return delim[c & 0x7f] != 0; };
   const int64_t total_bytes = offs[n];
   for (int64_t i = 0; i < total_bytes; ++i)
@@ -131,21 +131,19 @@ int64_t fmlx_tokenize_class(const char* bytes, const int64_t* offs, int64_t n, c
   return nt;
 }
 
-int64_t fmlx_tokenize_ws_lower(const char* bytes, const int64_t* offs, int64_t n, int32_t* ntok, int32_t* tok_ids,
-                               int64_t tok_cap, char* vocab_bytes, int64_t* vocab_offs, int64_t* nvocab) {
+FMLX_API int64_t fmlx_tokenize_ws_lower(const char* bytes, const int64_t* offs, int64_t n, int32_t* ntok,
+                                        int32_t* tok_ids, int64_t tok_cap, char* vocab_bytes, int64_t* vocab_offs,
+                                        int64_t* nvocab) {
   uint8_t ws[128] = {0};
   for (int c = 0; c < 128; ++c) ws[c] = java_ws((unsigned char)c) ? 1 : 0;
   return fmlx_tokenize_class(bytes, offs, n, ws, 0, 1, 0, ntok, tok_ids, tok_cap, vocab_bytes, vocab_offs, nvocab);
 }
-}
 
-extern "C" {
 // String.hashCode() of n strings given as UTF-16 code units (offs in units): s[0]·31^(n-1) + ...
-void fmlx_java_string_hashes(const uint16_t* units, const int64_t* offs, int64_t n, int32_t* out) {
+FMLX_API void fmlx_java_string_hashes(const uint16_t* units, const int64_t* offs, int64_t n, int32_t* out) {
   for (int64_t s = 0; s < n; ++s) {
     uint32_t h = 0;
     for (int64_t i = offs[s]; i < offs[s + 1]; ++i) h = 31u * h + units[i];
     out[s] = (int32_t)h;
   }
-}
 }

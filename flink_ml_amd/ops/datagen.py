@@ -16,19 +16,10 @@ import numpy as np
 import torch
 
 from . import native
-from .native import c_int, c_long, c_void_p
 
 _MULT = 0x5DEECE66D
 _ADD = 0xB
 _MASK = (1 << 48) - 1
-
-native.register_kernel_sigs({
-    "fmlx_java_int_draws": [native.c_ulonglong, native.c_ulonglong, c_long, c_int, c_void_p, c_void_p, c_void_p],
-    "fmlx_u8_zero_positions": [c_void_p, c_long, c_long, c_void_p, c_void_p, c_void_p],
-    "fmlx_remove_positions_i32": [c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p],
-    "fmlx_java_rows": [c_int, native.c_ulonglong, native.c_ulonglong, c_long, c_long, c_void_p, c_void_p, c_int, c_int,
-                       c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-})
 
 
 def scramble(seed: int) -> int:
@@ -184,10 +175,6 @@ def java_rows(seed: int, n: int, ops: Sequence[int], nvec: int, device=None, vec
         if device.type == "cuda":
             codes = java_uniform_int_rows(seed, n, len(ops), ops[0], device)
             return torch.empty((n, 0), dtype=vec_dtype, device=device), codes if int_codes else codes.to(torch.float64)
-        import ctypes
-
-        native.register_host_sigs({"fmlx_java_next_ints": [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                                           ctypes.c_void_p]})
         out = np.empty(n * len(ops), dtype=np.int32)
         native.host().fmlx_java_next_ints(int(seed), out.size, int(ops[0]), out.ctypes.data)
         return (torch.empty((n, 0), dtype=vec_dtype),
@@ -238,28 +225,6 @@ def java_rows(seed: int, n: int, ops: Sequence[int], nvec: int, device=None, vec
 # ---------------------------------------------------------------------------------------------
 # reservoir sampling (DataStreamUtils.SamplingOperator, DataStreamUtils.java:633-704) on device
 # ---------------------------------------------------------------------------------------------
-native.register_kernel_sigs({
-    "fmlx_java_next31": [native.c_ulonglong, native.c_ulonglong, c_long, c_void_p, c_void_p],
-    "fmlx_reservoir_final": [native.c_ulonglong, c_long, c_int, c_void_p, c_long, c_void_p, c_void_p],
-    "fmlx_reservoir_candidates": [c_void_p, c_long, c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p],
-})
-_host_sigs_done = False
-
-
-def _host_sigs():
-    global _host_sigs_done
-    if not _host_sigs_done:
-        import ctypes
-
-        native.register_host_sigs({
-            "fmlx_reservoir_rejections": ([ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p,
-                                           ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p],
-                                          ctypes.c_int64),
-            "fmlx_java_next31": [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p],
-        })
-        _host_sigs_done = True
-
-
 def next31_stream(seed: int, start: int, count: int, device) -> torch.Tensor:
     """Raw ``next(31)`` values of ``new Random(seed)`` at positions [start, start + count) (int32)."""
     out = torch.empty(max(int(count), 0), dtype=torch.int32, device=device)
@@ -269,7 +234,6 @@ def next31_stream(seed: int, start: int, count: int, device) -> torch.Tensor:
         native.call("fmlx_java_next31", scramble(seed), int(start), int(count), native.ptr(out),
                     native.stream_ptr(out.device))
     else:
-        _host_sigs()
         native.host().fmlx_java_next31(int(seed), int(start), int(count), out.data_ptr())
     return out
 
@@ -314,7 +278,6 @@ def reservoir_sample_device(n: int, k: int, seed: int, device) -> torch.Tensor:
         return torch.zeros(0, dtype=torch.int64, device=dev)
     if n <= k:
         return torch.arange(n, dtype=torch.int64, device=dev)
-    _host_sigs()
     m = n - k
     npos = m + m * n // (1 << 31) + 65536
     while True:

@@ -9,21 +9,13 @@ import math
 import torch
 
 from . import native
-from .native import c_int, c_long, c_void_p
-
-native.register_kernel_sigs({
-    "fmlx_dct_basis_shape": [c_int, c_void_p, c_void_p],
-    "fmlx_dct_rows": [c_void_p, c_long, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p],
-    "fmlx_dct_rows_f64": [c_void_p, c_long, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p],
-})
 
 
 def set_diag(diag: int = 0, per_cu: int = 0) -> None:
     """Diagnostics of the kernel's pipeline (1: skip the MFMAs, 2: skip the tile loads, 4: skip the
     stores; per_cu: cap on blocks per CU). Results are wrong while diag != 0."""
-    fn = native.kernels().fmlx_dct_set_diag
-    fn.restype = None
-    fn(int(diag), int(per_cu))
+    native.kernels().fmlx_dct_set_diag(int(diag), int(per_cu))
+
 
 MAX_N = 128
 

@@ -11,13 +11,6 @@ from typing import Dict, Optional
 import torch
 
 from . import native
-from .native import c_int, c_long, c_void_p
-
-native.register_kernel_sigs({
-    "fmlx_colstats": [c_int, c_void_p, c_long, c_long, c_int, c_void_p, c_int, c_void_p, c_void_p],
-    "fmlx_affine_cols": [c_int, c_int, c_void_p, c_long, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                         c_void_p],
-})
 
 
 def column_stats(X: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -66,11 +59,6 @@ def affine_cols(X: torch.Tensor, sub: Optional[torch.Tensor] = None, mul: Option
         out = out + add
     return out
 
-
-native.register_kernel_sigs({
-    "fmlx_group_colstats": [c_int, c_void_p, c_long, c_long, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
-                            c_void_p, c_void_p],
-})
 
 MAX_GROUPS = 32
 

@@ -2,7 +2,6 @@
 (``csrc/host/murmur3.cpp``) and a device kernel for large pre-encoded batches (``csrc/hash.hip``)."""
 from __future__ import annotations
 
-import ctypes
 import struct
 from typing import List, Sequence
 
@@ -10,16 +9,6 @@ import numpy as np
 import torch
 
 from . import native
-
-native.register_host_sigs({
-    "fmlx_murmur3_chars": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p], None),
-    "fmlx_murmur3_ints": ([ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p], None),
-    "fmlx_murmur3_longs": ([ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p], None),
-})
-native.register_kernel_sigs({
-    "fmlx_murmur3_chars_device": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_int,
-                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
-})
 
 
 def encode_utf16(strings: Sequence[str]):
@@ -91,13 +80,6 @@ def non_negative_mod(h: np.ndarray, mod: int) -> np.ndarray:
     return np.where(r < 0, r + mod, r)
 
 
-native.register_host_sigs({
-    "fmlx_hash_prefixed_doubles": [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                   ctypes.c_int32],
-    "fmlx_java_double_strings": [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p],
-})
-
-
 def hash_prefixed_doubles(prefix: str, vals: np.ndarray, nthreads: int = 0) -> np.ndarray:
     """murmur3_32(prefix + Double.toString(v)) for every value (native, multi-threaded)."""
     import os
@@ -112,10 +94,6 @@ def hash_prefixed_doubles(prefix: str, vals: np.ndarray, nthreads: int = 0) -> n
     return out
 
 
-native.register_kernel_sigs({
-    "fmlx_hash_prefixed_doubles_dev": [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
-                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
-})
 _RYU_TABLES = {}
 
 

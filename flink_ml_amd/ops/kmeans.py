@@ -13,29 +13,6 @@ import numpy as np
 import torch
 
 from . import native
-from .native import c_int, c_long, c_void_p
-
-native.register_kernel_sigs({
-    "fmlx_kmeans_set_sched": [c_int],
-    "fmlx_kmeans_assign_bf16": [c_void_p, c_long, c_long, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
-                                c_void_p, c_void_p],
-    "fmlx_kmeans_assign_generic": [c_int, c_void_p, c_long, c_long, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
-                                   c_void_p],
-    "fmlx_kmeans_chunk_sum": [c_int, c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p,
-                              c_void_p],
-    "fmlx_kmeans_cluster_sum": [c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
-    "fmlx_kmeans_chunk_sum_bf16v": [c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p,
-                                    c_void_p],
-    "fmlx_kmeans_offsets": [c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p],
-    "fmlx_sorted_bounds": [c_void_p, c_long, c_int, c_void_p, c_void_p],
-    "fmlx_kmeans_finalize": [c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                             c_void_p],
-    "fmlx_group_max_keys": [],
-    "fmlx_group_by_key": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "fmlx_group_stable_max_keys": [],
-    "fmlx_group_stable_scratch": ([c_long, c_int], c_long),
-    "fmlx_group_by_key_stable": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-})
 
 # rows grouped by cluster with the hand-written STABLE counting sort (csrc/groupsort.hip
 # st_*: per-tile histograms, column scan, ordered scatter — rows of a cluster stay in row order,

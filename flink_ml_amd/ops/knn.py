@@ -16,15 +16,6 @@ import os
 import torch
 
 from . import native
-from .native import c_int, c_long, c_void_p
-
-native.register_kernel_sigs({
-    "fmlx_knn_topk": [c_void_p, c_long, c_long, c_long, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                      c_void_p, c_void_p, c_void_p],
-    "fmlx_knn_fused": [c_void_p, c_long, c_long, c_int, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p,
-                       c_void_p, c_void_p, c_void_p],
-    "fmlx_knn_fused_blocks_per_cu": [c_int, c_int],
-})
 
 FUSED_MAX_K = 64
 FUSED_MAX_D = 128
@@ -164,10 +155,6 @@ def topk_from_products(G: torch.Tensor, qn: torch.Tensor, tn: torch.Tensor, k: i
 
 
 # ---- any k, fp32 or fp64: radix selection over a library-GEMM product block (csrc/knn_select.hip)
-native.register_kernel_sigs({
-    "fmlx_knn_select": [c_int, c_void_p, c_long, c_long, c_long, c_void_p, c_void_p, c_int, c_void_p, c_long,
-                        c_void_p],
-})
 SELECT_MAX_K = 8192  # csrc/knn_select.hip SEL_KMAX (the k winners are sorted in LDS)
 SELECT_BLOCK_BYTES = 1 << 30
 

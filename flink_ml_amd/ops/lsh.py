@@ -10,13 +10,8 @@ import torch
 
 from ..table import SparseColumn
 from . import native
-from .native import c_int, c_long, c_void_p
 
 HASH_PRIME = 2038074743
-
-native.register_kernel_sigs({
-    "fmlx_minhash_csr": [c_void_p, c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-})
 
 
 def to_csr_sets(X) -> SparseColumn:

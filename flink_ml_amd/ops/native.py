@@ -3,7 +3,9 @@
 The HIP kernels are plain ``extern "C"`` launchers that take device pointers and a
 ``hipStream_t``; we launch them onto torch's *current* HIP stream, so they order correctly
 with torch ops and RCCL collectives and can be captured into a hipGraph
-(``torch.cuda.CUDAGraph``) together with them.
+(``torch.cuda.CUDAGraph``) together with them. Every entry point's ctypes signature comes
+from its C definition (``build.api_signatures``, carried in the build manifest): nothing
+describes the ABI a second time in Python.
 
 Debugging: ``FMLX_SYNC_CHECK=1`` synchronises the device after every native launch and reports an
 asynchronous fault under the name of the kernel that caused it (the HIP analogue of a blocking
@@ -44,122 +46,14 @@ _TORCH2DT = {
     torch.int64: DT_I64,
 }
 
-c_void_p = ctypes.c_void_p
-c_int = ctypes.c_int
-c_long = ctypes.c_long
-c_ulonglong = ctypes.c_ulonglong
-c_double = ctypes.c_double
-c_float = ctypes.c_float
 
-# name -> argtypes (restype is always int: hipError_t, 0 == success)
-_KERNEL_SIGS = {
-    # glm.hip
-    "fmlx_glm_grad_partials": [c_int, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_int,
-                               c_long, c_int, c_void_p, c_void_p, c_int, c_void_p],
-    "fmlx_glm_round": [c_int, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_int,
-                       c_long, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                       c_int, c_double,
-                       c_double, c_double, c_double, c_void_p, c_int, c_int, c_void_p, c_void_p, c_long, c_int, c_int,
-                       c_int, c_int, c_void_p, c_void_p],
-    "fmlx_glm_round_wide": [c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_int, c_long,
-                            c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_double, c_double,
-                            c_double, c_double, c_void_p],
-    "fmlx_glm_set_tuning": [c_long, c_int],
-    "fmlx_glm_set_tail_tuning": [c_int, c_int],
-    "fmlx_glm_set_trace": ([c_void_p], None),
-    "fmlx_glm_cnt_elems": [],
-    "fmlx_glm_set_dma": [c_int],
-    "fmlx_glm_acc_elems": ([c_int], c_long),
-    "fmlx_glm_reduce_update": [c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                               c_double, c_double, c_double, c_double, c_void_p],
-    "fmlx_glm_reduce": [c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "fmlx_glm_update": [c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_double, c_double, c_double, c_double,
-                        c_void_p],
-    "fmlx_glm_predict": [c_int, c_int, c_int, c_void_p, c_long, c_long, c_int, c_void_p, c_int, c_double, c_void_p,
-                         c_void_p, c_void_p],
-    "fmlx_glm_grad_csr": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_long,
-                          c_int, c_void_p, c_void_p, c_void_p],
-    "fmlx_glm_csr_predict": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p],
-    "fmlx_glm_set_csc_tuning": [c_int, c_int],
-    "fmlx_glm_set_cell_xcd": ([c_int], None),
-    "fmlx_glm_wl_elems": [],
-    "fmlx_glm_csc_round": [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int,
-                           c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                           c_int, c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_int, c_int, c_int,
-                           c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                           c_void_p, c_void_p, c_void_p],
-    # glm_sparse.hip: single-visit bucket round
-    "fmlx_glm_bkt_limits": [c_void_p],
-    "fmlx_glm_sparse_set_trace": ([c_void_p], None),
-    "fmlx_glm_bkt_round": [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int,
-                           c_long, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double,
-                           c_double, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                           c_long, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "fmlx_glm_bkt_set_trace": ([c_void_p, c_long], None),
-    "fmlx_glm_bkt_count_all": [c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                               c_void_p, c_void_p, c_int, c_long, c_void_p],
-    # sort.hip
-    "fmlx_sorted_bounds": [c_void_p, c_long, c_int, c_void_p, c_void_p],
-    "fmlx_seg_sort_scratch": ([c_void_p, c_int, c_int, c_int], c_long),
-    "fmlx_seg_sort64": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
-                        c_long, c_void_p, c_void_p, c_long, c_void_p],
-    "fmlx_seg_sort32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
-                        c_long, c_void_p],
-    # csc_build.hip
-    "fmlx_csc_keys64": [c_void_p, c_void_p, c_void_p, c_long, c_long, c_long, c_int, c_long, c_void_p, c_void_p,
-                        c_int, c_void_p],
-    "fmlx_csc_keys": [c_void_p, c_void_p, c_long, c_long, c_long, c_int, c_long, c_void_p, c_void_p, c_void_p,
-                      c_void_p],
-    "fmlx_csc_fill": [c_int, c_void_p, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "fmlx_csc_sort_split": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
-                            c_long, c_void_p, c_void_p, c_long, c_void_p, c_long, c_int, c_void_p],
-    "fmlx_csc_colptr": [c_void_p, c_long, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p],
-    "fmlx_csc_tiles": [c_void_p, c_long, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_long,
-                       c_void_p],
-    "fmlx_csc_tiles_scratch": ([c_int, c_int], c_long),
-    "fmlx_csc_tile_keys": [c_int, c_void_p, c_long, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                           c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    "fmlx_csc_tile_store": [c_int, c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                            c_void_p],
-    "fmlx_cell_keys": [c_int, c_void_p, c_void_p, c_void_p, c_long, c_long, c_long, c_long, c_int, c_int, c_int, c_int,
-                       c_void_p, c_void_p, c_void_p],
-    "fmlx_cell_rekey": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p],
-    "fmlx_cell_store": [c_int, c_void_p, c_void_p, c_long, c_long, c_void_p, c_int, c_long, c_void_p, c_int, c_int,
-                        c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "fmlx_cell_bounds": [c_void_p, c_long, c_int, c_void_p, c_int, c_int, c_long, c_int, c_void_p, c_void_p],
-    # blas.hip set-up helpers
-    "fmlx_fill32": [c_void_p, c_long, ctypes.c_uint, c_void_p],
-    "fmlx_csr_batch_bounds": [c_void_p, c_long, c_long, c_long, c_void_p, c_void_p],
-    "fmlx_host_register": [c_void_p, c_long],
-    "fmlx_host_unregister": [c_void_p],
-    "fmlx_memcpy_h2d": [c_void_p, c_void_p, c_long, c_void_p],
-}
-
-_HOST_SIGS = {}
-
-
-def register_kernel_sigs(sigs: dict) -> None:
-    _KERNEL_SIGS.update(sigs)
-    if _KLIB is not None:
-        _apply_sigs(_KLIB, sigs)
-
-
-def register_host_sigs(sigs: dict) -> None:
-    _HOST_SIGS.update(sigs)
-    if _HLIB is not None:
-        _apply_sigs(_HLIB, sigs, restype=None)
-
-
-def _apply_sigs(lib, sigs, restype=c_int):
-    for name, spec in sigs.items():
-        fn = getattr(lib, name, None)
-        if fn is None:
-            continue
-        if isinstance(spec, tuple):
-            fn.argtypes, fn.restype = spec
-        else:
-            fn.argtypes = spec
-            fn.restype = restype
+def _bind(lib, api) -> None:
+    """Sets argtypes / restype of every entry point of ``lib`` from ``api`` (build.api_signatures:
+    derived from the C definitions; an entry point the library lacks is an error)."""
+    for name, (restype, argtypes) in api.items():
+        fn = getattr(lib, name)
+        fn.argtypes = [getattr(ctypes, a) for a in argtypes]
+        fn.restype = restype and getattr(ctypes, restype)
 
 
 def gpu_available() -> bool:
@@ -185,9 +79,9 @@ def kernels():
                     _build.build_kernels()
                 else:
                     raise RuntimeError("native kernel library missing: %s (run python -m flink_ml_amd.ops.build)" % path)
-            _build.check_fresh("kernels")  # never load a binary built from other sources
+            api = _build.check_fresh("kernels")  # never load a binary built from other sources
             lib = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
-            _apply_sigs(lib, _KERNEL_SIGS)
+            _bind(lib, api or _build.api_signatures("kernels"))  # (no manifest record: built by hand)
             _preload(lib)
             _KLIB = lib
     return _KLIB
@@ -202,12 +96,8 @@ def _preload(lib) -> None:
         return
     import time
 
-    fn = getattr(lib, "fmlx_preload_all", None)
-    if fn is None:
-        return
-    fn.argtypes, fn.restype = [c_void_p], c_int
     t0 = time.perf_counter()
-    k = fn(torch.cuda.current_stream().cuda_stream)
+    k = lib.fmlx_preload_all(torch.cuda.current_stream().cuda_stream)
     PRELOAD_MS = (time.perf_counter() - t0) * 1e3
     PRELOAD_STAGES["code_objects"] = round(PRELOAD_MS, 2)
     if k < 0:
@@ -218,18 +108,14 @@ def _preload(lib) -> None:
     hostsync.warm(torch.cuda.current_device())  # pinned read-back block + first-use imports
     PRELOAD_STAGES["pinned_readback"] = round((time.perf_counter() - t1) * 1e3, 2)
     t1 = time.perf_counter()
-    warm = getattr(lib, "fmlx_glm_sparse_warm", None)  # every sparse-round kernel launched once, dry
-    if warm is not None:
-        warm.argtypes, warm.restype = [c_void_p], c_int
-        if warm(torch.cuda.current_stream().cuda_stream) != 0:
-            raise RuntimeError("warming the sparse round kernels failed")
-        torch.cuda.current_stream().synchronize()
+    # every sparse-round kernel launched once, dry
+    if lib.fmlx_glm_sparse_warm(torch.cuda.current_stream().cuda_stream) != 0:
+        raise RuntimeError("warming the sparse round kernels failed")
+    torch.cuda.current_stream().synchronize()
     PRELOAD_STAGES["sparse_warm_launches"] = round((time.perf_counter() - t1) * 1e3, 2)
     torch.cuda.get_device_properties(torch.cuda.current_device())  # (first call: runtime queries)
     # the bucket round's compile-time limits, read here (a first fit paid ~50 µs for the first call
     # of the entry point); through ``lib``: kernels() holds its lock until this returns
-    # (no package import here: a module imported inside this lock could register signatures that
-    # _apply_sigs has already passed)
     global BKT_LIMITS
     import numpy as np
 
@@ -260,10 +146,9 @@ def host():
             path = os.environ.get("FMLX_HOST_LIB") or _build.HOST_LIB
             if not os.path.exists(path):
                 _build.build_host()
-            if path == _build.HOST_LIB:
-                _build.check_fresh("host")
+            api = _build.check_fresh("host") if path == _build.HOST_LIB else None
             lib = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
-            _apply_sigs(lib, _HOST_SIGS, restype=None)
+            _bind(lib, api or _build.api_signatures("host"))  # (no manifest record, or FMLX_HOST_LIB)
             _HLIB = lib
     return _HLIB
 

@@ -17,12 +17,6 @@ import torch
 
 from ..parallel import comm
 from . import native
-from .native import c_int, c_long, c_void_p
-
-native.register_kernel_sigs({
-    "fmlx_radix_hist": [c_int, c_void_p, c_long, c_long, c_int, c_void_p, c_int, c_int, c_int, c_long, c_void_p,
-                        c_void_p, c_void_p],
-})
 
 _BITS = 11
 _MAXQ = 4  # quantiles per kernel pass (LDS histogram [Q][16][256])

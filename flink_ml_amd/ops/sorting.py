@@ -10,17 +10,6 @@ import numpy as np
 import torch
 
 from . import native
-from .native import c_double, c_int, c_long, c_void_p
-
-native.register_kernel_sigs({
-    "fmlx_sort_bits_scratch": ([c_void_p, c_int, c_int], c_long),
-    "fmlx_sort_u64": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_long,
-                      c_void_p],
-    "fmlx_bc_tile": [],
-    "fmlx_bc_keys": [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p],
-    "fmlx_bc_metrics": [c_void_p, c_void_p, c_void_p, c_long, c_double, c_double, c_double, c_double,
-                        c_void_p, c_void_p, c_void_p, c_void_p],
-})
 
 U64 = torch.int64  # uint64 keys live in int64 storage (bit patterns; never compared by torch)
 

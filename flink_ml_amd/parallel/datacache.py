@@ -31,22 +31,6 @@ import torch
 from ..ops import native
 from ..table import SparseColumn, Table
 
-_P, _I = ctypes.c_void_p, ctypes.c_int64
-native.register_host_sigs({
-    "fmlx_dc_open": ([ctypes.c_char_p, _I, _I], ctypes.c_void_p),
-    "fmlx_dc_append": ([_P, _P, _I], ctypes.c_int64),
-    "fmlx_dc_num_records": ([_P], ctypes.c_int64),
-    "fmlx_dc_record_size": ([_P, _I], ctypes.c_int64),
-    "fmlx_dc_read": ([_P, _I, _P], ctypes.c_int),
-    "fmlx_dc_spill_all": ([_P], ctypes.c_int),
-    "fmlx_dc_stats": ([_P, _P], None),
-    "fmlx_dc_finish": ([_P], ctypes.c_int),
-    "fmlx_dc_reopen": ([ctypes.c_char_p], ctypes.c_void_p),
-    "fmlx_dc_close": ([_P, ctypes.c_int], None),
-    "fmlx_dc_record_ptr": ([_P, _I], ctypes.c_void_p),
-    "fmlx_dc_segment_mem": ([_P, _I, _P], ctypes.c_void_p),
-})
-
 DEFAULT_SEGMENT_BYTES = 1 << 30          # reference DataCacheWriter: segments up to 1 GB
 DEFAULT_MEMORY_BUDGET = 8 << 30
 

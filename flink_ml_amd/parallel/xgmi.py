@@ -35,31 +35,7 @@ import torch
 import torch.distributed as dist
 
 from ..ops import native
-from ..ops.native import c_int, c_long, c_void_p
 from .context import get_context
-
-native.register_kernel_sigs({
-    "fmlx_xar_total_bytes": ([], c_long),
-    "fmlx_xar_chunk": [],
-    "fmlx_xar_max_blocks": [],
-    "fmlx_xar_max_ranks": [],
-    "fmlx_xar_gen_size": [],
-    "fmlx_xar_glm_max": [],
-    "fmlx_xar_handle_size": [],
-    "fmlx_xar_alloc": [c_long, c_void_p, c_void_p],
-    "fmlx_xar_open": [c_void_p, c_void_p],
-    "fmlx_xar_close": [c_void_p],
-    "fmlx_xar_free": [c_void_p],
-    "fmlx_host_flags_alloc": [c_int, c_void_p, c_void_p],
-    "fmlx_host_flags_free": [c_void_p],
-    "fmlx_xar_allreduce": [c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p,
-                           c_long, c_void_p],
-    "fmlx_xar_allreduce2": [c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p,
-                            c_long, c_void_p],
-    "fmlx_xar_twoshot_max": ([], c_long),
-    "fmlx_xar_strict_fence": [],
-    "fmlx_xar_set_strict_fence": [c_int],
-})
 
 
 def strict_fence() -> bool:
@@ -94,7 +70,7 @@ class HostFlags:
 
     def __init__(self, n: int = 1):
         lib = native.kernels()
-        h, d = c_void_p(), c_void_p()
+        h, d = ctypes.c_void_p(), ctypes.c_void_p()
         rc = lib.fmlx_host_flags_alloc(int(n), ctypes.byref(h), ctypes.byref(d))
         if rc != 0:
             raise RuntimeError("hipHostMalloc of the status words failed (%d)" % rc)
@@ -110,7 +86,7 @@ class HostFlags:
 
     def close(self) -> None:
         if self.host:
-            self.lib.fmlx_host_flags_free(c_void_p(self.host))
+            self.lib.fmlx_host_flags_free(ctypes.c_void_p(self.host))
             self.host = None
 
 
@@ -134,7 +110,7 @@ class XgmiComm:
         self._opened = []
         hs = lib.fmlx_xar_handle_size()
         handle = ctypes.create_string_buffer(hs)
-        base = c_void_p()
+        base = ctypes.c_void_p()
         rc = -1
         try:
             with torch.cuda.device(self.device):
@@ -155,7 +131,7 @@ class XgmiComm:
             if r == self.rank:
                 ptrs.append(self._base)
                 continue
-            p = c_void_p()
+            p = ctypes.c_void_p()
             if ok and lib.fmlx_xar_open(ctypes.create_string_buffer(h, len(h)), ctypes.byref(p)) == 0 and p.value:
                 ptrs.append(p.value)
                 self._opened.append(p.value)
@@ -231,10 +207,10 @@ class XgmiComm:
         if getattr(self, "err", None) is not None:
             self.err.close()
         for p in self._opened:
-            self.lib.fmlx_xar_close(c_void_p(p))
+            self.lib.fmlx_xar_close(ctypes.c_void_p(p))
         self._opened = []
         if self._base:
-            self.lib.fmlx_xar_free(c_void_p(self._base))
+            self.lib.fmlx_xar_free(ctypes.c_void_p(self._base))
             self._base = None
 
 

@@ -32,22 +32,12 @@ def java_string_hash(s: str) -> int:
     return _i32(h)
 
 
-_HASH_SIG = False
-
-
 def java_string_hashes(strings) -> "np.ndarray":
     """``String.hashCode()`` of many strings at once (native loop over their UTF-16 units)."""
-    import ctypes
-
     import numpy as np
 
     from ..ops import native
 
-    global _HASH_SIG
-    if not _HASH_SIG:
-        native.register_host_sigs({"fmlx_java_string_hashes": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                                               ctypes.c_void_p]})
-        _HASH_SIG = True
     strings = list(strings)
     n = len(strings)
     out = np.zeros(n, dtype=np.int32)
@@ -253,16 +243,11 @@ class JavaRandom:
 
 def java_random_doubles(seed: int, n: int):
     """``n`` successive ``new Random(seed).nextDouble()`` values (native host loop)."""
-    import ctypes
-
     import numpy as np
 
     from ..ops import native
 
     out = np.empty(n, dtype=np.float64)
     if n:
-        lib = native.host()
-        fn = lib.fmlx_java_next_doubles
-        fn.argtypes, fn.restype = [ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p], None
-        fn(int(seed), int(n), out.ctypes.data)
+        native.host().fmlx_java_next_doubles(int(seed), int(n), out.ctypes.data)
     return out

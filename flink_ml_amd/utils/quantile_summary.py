@@ -11,21 +11,11 @@ insertion, compression, merge and query — run in native C++ (``ops/csrc/host/g
 """
 from __future__ import annotations
 
-import ctypes
 from typing import List, Sequence, Union
 
 import numpy as np
 
 from ..ops import native
-
-_P = ctypes.c_void_p
-_I = ctypes.c_int64
-native.register_host_sigs({
-    "fmlx_gk_insert": ([_P, _P, _P, _I, _P, _I, _I, _P, _P, _P], ctypes.c_int64),
-    "fmlx_gk_compress": ([_P, _P, _P, _I, ctypes.c_double, _P, _P, _P], ctypes.c_int64),
-    "fmlx_gk_merge": ([_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P], ctypes.c_int64),
-    "fmlx_gk_query": ([_P, _P, _P, _I, _I, ctypes.c_double, _P, _I, _P], None),
-})
 
 DEFAULT_HEAD_SIZE = 50000
 DEFAULT_COMPRESS_THRESHOLD = 10000

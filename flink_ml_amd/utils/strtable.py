@@ -11,29 +11,14 @@ those is one native batch call over the code-unit array (``ops/csrc/host/strtab.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import List, Optional, Sequence
 
 import numpy as np
 
-_SIGS = False
-
 
 def _lib():
-    global _SIGS
     from ..ops import native
 
-    if not _SIGS:
-        vp, i64 = ctypes.c_void_p, ctypes.c_int64
-        native.register_host_sigs({
-            "fmlx_str_hash64": [vp, vp, i64, vp],
-            "fmlx_str_argsort": [vp, vp, i64, ctypes.c_int, vp],
-            "fmlx_str_lookup": [vp, vp, i64, vp, vp, i64, vp],
-            "fmlx_java_string_hashes": [vp, vp, i64, vp],
-            "fmlx_hashmap_order": [vp, i64, i64, vp],
-            "fmlx_str_gather": [vp, vp, vp, i64, vp, vp],
-        })
-        _SIGS = True
     return native.host()
 
 

@@ -222,3 +222,21 @@ def test_device_sgd_misaligned_width_padded_to_fused_kernel(dtype, d):
         gemv = DeviceGlmTrainer(sgd, np.zeros(d), X.cuda(), y.cuda(), w.cuda(), loss, pad=False)
         if gemv.wide:
             assert np.abs(gemv.fit() - got).max() < tol
+
+
+def test_kernel_library_exports_every_derived_entry_point():
+    """Every entry point parsed from csrc/*.hip resolves in the loaded library with the derived
+    signature, and the load itself read the bucket round's limits through one of them."""
+    _need_gpu()
+    import ctypes
+
+    from flink_ml_amd.ops import build, native
+
+    lib = native.kernels()
+    api = build.api_signatures("kernels")
+    assert len(api) > 100
+    for name, (restype, argtypes) in api.items():
+        fn = getattr(lib, name)  # AttributeError: parsed but not exported
+        assert list(fn.argtypes) == [getattr(ctypes, a) for a in argtypes], name
+        assert fn.restype is (getattr(ctypes, restype) if restype else None), name
+    assert native.BKT_LIMITS is not None and native.BKT_LIMITS.shape == (8,) and native.BKT_LIMITS.any()

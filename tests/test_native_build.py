@@ -20,8 +20,10 @@ def test_manifest_records_sources_and_build_outcome():
     assert k["source_digest"] == b.source_digest("kernels")
     assert set(k["compiled"]) | set(k["reused"]) == {os.path.basename(s) for s in b.kernel_sources()[0]}
     assert man["host"]["source_digest"] == b.source_digest("host")
-    b.check_fresh("kernels")
-    b.check_fresh("host")
+    # the entry points' signatures, as parsed at build time, travel with the digest they belong to
+    for which in ("kernels", "host"):
+        assert man[which]["api"] == json.loads(json.dumps(b.api_signatures(which)))
+        assert b.check_fresh(which) == man[which]["api"]
 
 
 def test_stale_library_is_refused(monkeypatch):
