@@ -471,8 +471,15 @@ __device__ __forceinline__ void dma16_nt(const void* g, unsigned lds) {
 // on the flagship shape — a dynamic chunk-claim schedule, claimed row pairs after a static prefix,
 // per-XCD L2 accumulator replicas, and a tail prefetch of the next round's rows; all exact, all
 // slower: profiles/r3/lr_{dyn_schedule,pair_schedule,l2acc,tail_prefetch_timegated}_ab_1gpu.jsonl.)
+//
+// DEPTH selects the row path: 0 = the register loop above, 2–4 = a per-wave LDS-DMA ring of DEPTH
+// steps, LOADER (−1) = WPB consumer waves plus one loader wave that streams the block's rows
+// through a ring of LOADER_SLOTS 16-KiB slots (see the path's own comment).
+constexpr int LOADER = -1;
+constexpr int LOADER_SLOTS = 4;
+constexpr int LOADER_SLOT_BYTES = 16384;  // 8 rows × 2 KiB
 template <typename T, int EPC, int CPL, int U, int WPB, bool NT, int DEPTH = 0>
-__global__ __launch_bounds__(WPB * 64, (glm_min_waves<T, EPC, CPL, U>())) void glm_round_kernel(
+__global__ __launch_bounds__((WPB + (DEPTH < 0 ? 1 : 0)) * 64, (DEPTH < 0 ? 1 : glm_min_waves<T, EPC, CPL, U>())) void glm_round_kernel(
     const T* X, long ld, const typename AccOf<T>::type* y,
     const typename AccOf<T>::type* wt, typename AccOf<T>::type* coef,
     long n, int d, long B, int loss, int* state, typename AccOf<T>::type* partials, GlmTail tl) {
@@ -743,6 +750,109 @@ __global__ __launch_bounds__(WPB * 64, (glm_min_waves<T, EPC, CPL, U>())) void g
     }
     // the epilogue's LDS buffers alias the ring: every wave of the block is past its last read
     __syncthreads();
+  } else if constexpr (DEPTH < 0) {
+    // ---- Loader/consumer row path (bf16 rows of 65–128 16-byte chunks, U = 1). The block is WPB
+    // consumer waves plus one loader wave (wave WPB). Consumer wave q still owns rows
+    // start + b·WPB + q + j·W, j ascending, so labels, row census and per-wave accumulation order
+    // are the register loop's. Step j's WPB consecutive rows of the block form one 16-KiB ring
+    // slot, filled by the loader with 16 one-KiB LDS-DMA loads: the 16·d contiguous bytes of the
+    // group where the rows are dense (ld == d) and the whole group lies inside the batch (row
+    // pitch 2·d in the slot), else two pieces per row at a 2-KiB pitch (rows past the batch end
+    // re-read the group's first row and are masked; lanes past the last chunk re-read it).
+    // One phase per step, one raw s_barrier per phase (never __syncthreads(): it would drain the
+    // DMA). Phase k: the loader issues step k + S − 2 into the slot read in phase k − 2 — those
+    // ds_reads retired (lgkmcnt(0)) before the readers reached phase k − 1's barrier, which the
+    // loader has passed — then waits with a counted vmcnt until step k has landed, then the
+    // barrier; the consumers read step k's slot only after that barrier. S − 2 fills are issued
+    // before the deferred prologue, so the ring fills while the prologue runs. vmcnt counts at
+    // most 63 loads: 16·(S − 1) = 48 outstanding at most with S = 4.
+    // (scripts/stream_probe_loader.hip, profiles/r7/lr_probe_loader.log: this structure with the
+    // round's math streams a 200 MB batch in 31.3–31.6 µs on 224 blocks; the register loop with no
+    // math at all takes 32.2–32.6.)
+    static_assert(sizeof(T) == 2 && EPC == 8 && CPL == 2 && U == 1, "loader path: bf16 rows of 65-128 chunks, U = 1");
+    constexpr int S = LOADER_SLOTS;
+    constexpr int PIECES = 2 * WPB;  // DMA loads per slot
+    static_assert(PIECES * (S - 1) <= 63, "vmcnt counts 63 loads");
+    extern __shared__ __align__(16) unsigned char smem_r[];
+    typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(3))) u32x4_t lds_u4_t;
+    unsigned char* ring = smem_r + tl.ring_off;
+    const unsigned ring_a = __builtin_amdgcn_readfirstlane((unsigned)(size_t)ring);
+    const bool loader = wave == WPB;
+    const long rb0 = start + (long)blockIdx.x * WPB;          // the block's first row
+    const long nj = rb0 < end ? (end - rb0 + W - 1) / W : 0;  // steps of this block (block-uniform)
+    const bool dense = ld == (long)d;
+    const int c1 = lane + 64 < nch ? lane + 64 : nch - 1;
+    auto fill = [&](long k) {
+      const unsigned base = ring_a + (unsigned)(k % S) * LOADER_SLOT_BYTES;
+      const long rb = rb0 + k * W;  // < end for k < nj
+      if (dense && rb + WPB <= end) {
+        const T* g = X + rb * ld;
+        const int last = WPB * nch - 1;
+#pragma unroll
+        for (int i = 0; i < PIECES; ++i) {
+          const int c = i * 64 + lane < last ? i * 64 + lane : last;
+          dma16_nt(g + (long)c * EPC, base + i * 1024u);
+        }
+      } else {
+#pragma unroll
+        for (int u = 0; u < WPB; ++u) {
+          const long ru = rb + u < end ? rb + u : rb;
+          const T* row = X + ru * ld;
+          dma16_nt(row + lane * EPC, base + u * 2048u);
+          dma16_nt(row + c1 * EPC, base + u * 2048u + 1024u);
+        }
+      }
+    };
+    if (loader) {
+#pragma unroll
+      for (int k = 0; k < S - 2; ++k)
+        if (k < nj) fill(k);
+    } else if (nj > 0) {
+      load_labels(0);
+    }
+    if (tl.defer && (tl.mode == TAIL_XGMI ? defer_prologue_xgmi<A>(tl, coef, state, e, d, wdef)
+                                          : defer_prologue<A>(tl, coef, state, e, d, wdef))) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA may land after the wave exits
+      return;
+    }
+    if (nj > 0) {
+      if (loader) {
+        for (long k = 0; k < nj; ++k) {
+          if (k + S - 2 < nj) {
+            fill(k + S - 2);
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PIECES * (S - 2)) : "memory");  // step k landed
+          } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          }
+          __builtin_amdgcn_s_barrier();
+        }
+      } else {
+        load_w();
+        for (long k = 0; k < nj; ++k) {
+          __builtin_amdgcn_s_barrier();
+          asm volatile("" ::: "memory");
+          if ((k & 63) == 0 && k > 0) load_labels(k);
+          const long rb = rb0 + k * W;
+          const unsigned pitch = dense && rb + WPB <= end ? 2u * (unsigned)d : 2048u;
+          const unsigned char* row = ring + (k % S) * LOADER_SLOT_BYTES + wave * pitch;
+          const u32x4_t v0 = *(const lds_u4_t*)(row + lane * 16);
+          const u32x4_t v1 = *(const lds_u4_t*)(row + c1 * 16);
+          // retired before the next barrier: the slot is refilled one phase after it
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          __builtin_amdgcn_sched_barrier(0);
+          __builtin_memcpy(xa[0][0].v, &v0, 16);
+          __builtin_memcpy(xa[0][1].v, &v1, 16);
+          va[0] = rb + wave < end;
+          ya[0] = lane_val(ylab, (int)(k & 63));
+          wa[0] = lane_val(wlab, (int)(k & 63));
+          process(xa, ya, wa, va);
+        }
+      }
+    }
+    // the epilogue's LDS buffers alias the ring: the loader has drained its DMA (vmcnt(0) in its
+    // last phases) and every consumer is past its last read
+    __syncthreads();
   } else {
   const long step = (long)U * W;
   long r = start + gw;
@@ -825,7 +935,8 @@ __global__ __launch_bounds__(WPB * 64, (glm_min_waves<T, EPC, CPL, U>())) void g
   const bool flat = tl.mode != TAIL_PARTIALS && !tl.det && tl.flat_lds;
   A* lw = buf + (flat ? WPB : WPB / 2) * (long)d;   // [WPB][2]
   int* sflag = reinterpret_cast<int*>(lw + WPB * 2);
-  if (lane == 0) { lw[wave * 2] = wsum; lw[wave * 2 + 1] = lsum; }
+  const bool worker = DEPTH >= 0 || wave < WPB;  // the loader wave holds no sums
+  if (lane == 0 && worker) { lw[wave * 2] = wsum; lw[wave * 2 + 1] = lsum; }
   if (flat) {
     // atomic tail, one barrier: every wave parks its row in LDS, then each thread sums its
     // columns over the waves (fixed order) and adds them to tl.acc (256 contiguous bytes per
@@ -834,7 +945,7 @@ __global__ __launch_bounds__(WPB * 64, (glm_min_waves<T, EPC, CPL, U>())) void g
 #pragma unroll
     for (int k = 0; k < CPL; ++k) {
       const int c = lane + 64 * k;
-      if (c < nch)
+      if (c < nch && worker)
 #pragma unroll
         for (int i = 0; i < EPC; ++i) mine[c * EPC + i] = acc[k][i];
     }
@@ -1247,7 +1358,10 @@ static int g_acc_reps = 4;  // atomic-tail accumulator replicas (A/B knob, <= AC
 static int g_ticket2 = 0;   // two-level tickets (A/B knob)
 static long long* g_trace = nullptr;  // per-block timestamps of the next launches (diagnostics)
 
-static int g_dma_depth = 0;  // LDS-DMA row ring depth in steps (0 = 16-byte register loads)
+// row path of the fused round: −1 = automatic (the loader/consumer path where it applies, else
+// register loads), 0 = 16-byte register loads, 2–4 = per-wave LDS-DMA ring of that many steps
+static int g_dma_depth = -1;
+static int g_row_path = 0;  // row path of the last fused-round launch (−1 loader, 0 registers, 2–4 ring)
 
 template <typename T, int EPC, int CPL, int U, int DEPTH>
 int launch_grad_k(const void* X, long ld, const void* y, const void* wt, void* coef, long n, int d, long B, int loss,
@@ -1256,7 +1370,8 @@ int launch_grad_k(const void* X, long ld, const void* y, const void* wt, void* c
   // epilogue LDS: [WPB or WPB/2][d] wave rows | [WPB][2] | ticket flag; the DMA ring (if any)
   // starts at 0 and the epilogue buffers alias it; the deferred mode's w image follows both
   const size_t tail = (size_t)(t2.flat_lds ? WPB : WPB / 2) * d * sizeof(A) + WPB * 2 * sizeof(A) + 16;
-  const size_t ring = (size_t)WPB * DEPTH * U * 2048;
+  const size_t ring = DEPTH < 0 ? (size_t)LOADER_SLOTS * LOADER_SLOT_BYTES : (size_t)WPB * DEPTH * U * 2048;
+  constexpr int NW = WPB + (DEPTH < 0 ? 1 : 0);  // the loader path adds its loader wave
   size_t shmem = tail > ring ? tail : ring;
   t2.ring_off = 0;
   if (t2.defer) {
@@ -1279,7 +1394,7 @@ int launch_grad_k(const void* X, long ld, const void* y, const void* wt, void* c
   if (shmem > (size_t)LDS_PER_CU) return -8;
   if constexpr (EPC * sizeof(T) == 16 && sizeof(T) == 2) {
     if (nt) {
-      hipLaunchKernelGGL((glm_round_kernel<T, EPC, CPL, U, WPB, true, DEPTH>), dim3(nblocks), dim3(WPB * 64), shmem, s,
+      hipLaunchKernelGGL((glm_round_kernel<T, EPC, CPL, U, WPB, true, DEPTH>), dim3(nblocks), dim3(NW * 64), shmem, s,
                          (const T*)X, ld, (const A*)y, (const A*)wt, (A*)coef, n, d, B, loss, state, (A*)partials, t2);
       return (int)hipGetLastError();
     }
@@ -1306,7 +1421,17 @@ int launch_grad_u(const void* X, long ld, const void* y, const void* wt, void* c
   // LDS-DMA ring: bf16 rows of 65–128 16-byte chunks (d 513–1024), 16-byte aligned, non-temporal
 #ifndef FMLX_ISA_PROBE_U
   if constexpr (sizeof(T) == 2 && EPC == 8 && CPL == 2) {
+    // automatic: the loader/consumer path for streamed (non-temporal) batches on at most one
+    // block per CU, when its LDS fits (launch_grad_k answers −8 before launching if it does not).
+    // 36.6–36.9 vs 38.4–38.5 µs per round, profiles/r7/lr_loader_ab_1gpu.jsonl. MALL-resident data
+    // (default-policy loads) keeps the register loop: the path was only measured with nt fills.
+    if (g_dma_depth < 0 && nt && nblocks <= NUM_CU) {
+      const int rc = launch_grad_k<T, EPC, CPL, 1, LOADER>(X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, t2, nt, s);
+      g_row_path = LOADER;
+      if (rc != -8) return rc;
+    }
     if (g_dma_depth > 0 && nt) {
+      g_row_path = g_dma_depth < 4 ? g_dma_depth : 4;
       switch (g_dma_depth) {
         case 2: return launch_grad_k<T, EPC, CPL, U, 2>(X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, t2, nt, s);
         case 3: return launch_grad_k<T, EPC, CPL, U, 3>(X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, t2, nt, s);
@@ -1315,6 +1440,7 @@ int launch_grad_u(const void* X, long ld, const void* y, const void* wt, void* c
     }
   }
 #endif
+  g_row_path = 0;
   return launch_grad_k<T, EPC, CPL, U, 0>(X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, t2, nt, s);
 }
 
@@ -1430,12 +1556,16 @@ FMLX_API void fmlx_glm_set_trace(void* trace) {
 // ints of the fused round's counter block: the arrival tickets (TAIL_TOP + 1, padded to 128)
 FMLX_API int fmlx_glm_cnt_elems() { return 128; }
 
-// LDS-DMA row ring of the fused round (bf16 rows of d 513–1024): depth in steps, 0 = off
+// Row path of the fused round (bf16 rows of d 513–1024): −1 = automatic (loader/consumer path
+// for streamed batches), 0 = register loads, 2–4 = per-wave LDS-DMA ring of that many steps
 FMLX_API int fmlx_glm_set_dma(int depth) {
-  if (depth < 0 || depth > 4 || depth == 1) return -1;
+  if (depth < -1 || depth > 4 || depth == 1) return -1;
   g_dma_depth = depth;
   return 0;
 }
+
+// which row path the last fused-round launch of this process took (tests, A/B scripts)
+FMLX_API int fmlx_glm_row_path() { return g_row_path; }
 
 FMLX_API int fmlx_glm_set_tail_tuning(int acc_reps, int ticket2) {
   if (acc_reps < 1 || acc_reps > ACC_MAX_REPS) return -1;

@@ -31,6 +31,9 @@ GRAD_UNROLL = int(os.environ.get("FMLX_GLM_UNROLL", "0"))
 # 1000) take 4 rows in flight per wave on 224 blocks (28 per XCD): 37.31 us per round vs 38.56 on
 # 256 blocks and 39.75 for U=1 on 512, interleaved on one MI355X (profiles/r3/lr_unroll_grid_*,
 # lr_unroll2_grid_*; bench.py 39.5 vs 40.8 us per step)
+# round 7: the same 224 blocks carry the loader/consumer path (DMA_DEPTH below; 8 consumer waves +
+# 1 loader wave per block): 36.7 us per round vs 39.1 on 256 blocks and 38.5 for the register loop
+# on 224 (profiles/r7/lr_loader_ab_1gpu.jsonl)
 GRAD_BLOCKS = int(os.environ.get("FMLX_GLM_BLOCKS", "0"))
 
 
@@ -63,16 +66,31 @@ def set_tail_tuning(acc_reps: int = 4, ticket2: bool = False) -> None:
     native.call("fmlx_glm_set_tail_tuning", int(acc_reps), int(bool(ticket2)))
 
 
-# LDS-DMA row ring of the fused round (csrc/glm.hip, DEPTH): bf16 rows of d 513–1024 stream into a
-# per-wave LDS ring by global_load_lds (DEPTH − 1 steps of U rows in flight through the math).
-# FMLX_GLM_DMA = ring depth in steps (0 = 16-byte register loads).
-DMA_DEPTH = int(os.environ.get("FMLX_GLM_DMA", "0"))
+# Row path of the fused round for bf16 rows of d 513–1024 (csrc/glm.hip, DEPTH). FMLX_GLM_DMA:
+#  -1  automatic (default): streamed batches (non-temporal loads) on at most one block per CU take
+#      the loader/consumer path — a ninth wave per block fills a ring of four 16-KiB LDS slots (one
+#      step's 8 consecutive rows each) by global_load_lds behind a counted vmcnt, and hands each
+#      slot to the 8 consumer waves over one raw s_barrier per step; the consumers keep the register
+#      loop's row -> (block, wave, order) mapping and math, at 112 VGPRs instead of 148. Everything
+#      else takes register loads. Grid: round_blocks (224 for this layout).
+#      Streaming probe profiles/r7/lr_probe_loader.log; kernel and driver A/B against
+#      FMLX_GLM_DMA=0 profiles/r7/lr_loader_ab_1gpu.jsonl, lr_bench_loader_ab.log
+#   0  16-byte register loads, two steps of U rows per wave in flight (the round 3–6 kernel)
+# 2–4  per-wave LDS-DMA ring of that many steps (round 4; slower: every wave issues its own DMA
+#      between its own math, profiles/r4/lr_lds_dma_ring_ab_1gpu.jsonl)
+DMA_DEPTH = int(os.environ.get("FMLX_GLM_DMA", "-1"))
 
 
 def set_dma(depth: int) -> None:
-    """Ring depth of the fused round's LDS-DMA row path (0 = off; 2–4 steps)."""
+    """Row path of the fused round: -1 = automatic (loader/consumer path for streamed batches),
+    0 = register loads, 2–4 = per-wave LDS-DMA ring of that many steps."""
     if native.kernels().fmlx_glm_set_dma(int(depth)) != 0:
-        raise ValueError("depth must be 0, 2, 3 or 4")
+        raise ValueError("depth must be -1, 0, 2, 3 or 4")
+
+
+def row_path() -> int:
+    """Row path the last fused-round launch took: -1 loader/consumer, 0 register loads, 2–4 ring."""
+    return int(native.kernels().fmlx_glm_row_path())
 
 
 def set_trace(buf: Optional[torch.Tensor]) -> None:

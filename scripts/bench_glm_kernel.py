@@ -5,7 +5,8 @@
 Variants: ``u`` (rows in flight per wave = 2u), ``b`` (blocks = partial rows), ``split``
 (legacy 3-launch round: grad partials → stage-1 → reduce+update) vs the fused one-launch round,
 ``defer`` (0: ticketed atomic tail; 1: round e − 1 completed in launch e's prologue), ``dma``
-(LDS-DMA row ring depth in steps, 0 = register loads).
+(row path: -1 = automatic, i.e. the loader/consumer path for streamed batches; 0 = register
+loads, the default here; 2–4 = per-wave LDS-DMA ring of that many steps).
 Usage: python scripts/bench_glm_kernel.py --configs "u=2,b=512;u=4,b=256;split=1"
 """
 import argparse
@@ -69,7 +70,10 @@ def main():
     y = torch.randint(0, 2, (a.rows,), generator=g, device=dev).float()
     cfgs = parse(a.configs)
     res = {json.dumps(c): [] for c in cfgs}
-    for rep in range(a.reps):
+    # repetition -1 is a warm-up pass over every configuration and is not recorded: the first pass
+    # of a process loads code objects, captures the graphs and ramps the clocks (its 7.6 ms window
+    # read 3–6 µs per round high on whichever configuration came first)
+    for rep in range(-1, a.reps):
         for c in cfgs:
             gk.GRAD_UNROLL = c.get("u", 0)
             gk.GRAD_BLOCKS = c.get("b", 512)
@@ -94,12 +98,14 @@ def main():
             us = (time.perf_counter() - t0) / a.rounds * 1e6
             # deferred rounds: the last launch's round completes in the next launch
             assert c.get("m0") or tr.rounds_executed() == 20 + a.rounds - int(tr.defer)
-            res[json.dumps(c)].append(us)
+            if rep >= 0:
+                res[json.dumps(c)].append(us)
     gb = a.batch * a.dim * 2 / 1e9
     for k, v in res.items():
         med = statistics.median(v)
         print(json.dumps({"config": json.loads(k), "ld": ld, "us_per_round_median": round(med, 2),
-                          "us_min": round(min(v), 2), "samples_per_s": round(a.batch / med * 1e6),
+                          "us_min": round(min(v), 2), "us_max": round(max(v), 2),
+                          "us_reps": [round(x, 2) for x in v], "samples_per_s": round(a.batch / med * 1e6),
                           "batch_TB_per_s": round(gb / med * 1e6 / 1e3, 3)}), flush=True)
 
 
