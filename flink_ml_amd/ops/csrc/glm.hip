@@ -6,29 +6,51 @@
 // RegularizationUtils.java:47-91.
 //
 // MI355X design
-//  * glm_grad_partials: ONE pass over the minibatch rows in HBM. A wave owns a row at a
-//    time (two rows in flight for ILP when registers allow); each lane owns a fixed set of
-//    EPC-element chunks (16-byte loads), so the coefficient slice AND the gradient
-//    accumulator for those columns live in that lane's registers for the whole kernel: the
-//    row is read exactly once, dot → wave butterfly → loss/multiplier → axpy, no LDS, no
-//    atomics. Waves of a block combine by a fixed-order LDS tree, each block writes one
-//    partial row [grad(d) | Σweight | Σloss] → deterministic, bit-reproducible.
-//  * The round's reduction is fused into the same launch (glm_round_tail): each block publishes
-//    its partial row and draws an arrival ticket (agent-scope release/acquire, Guideline 16);
-//    the last block of every group of 32 sums the group's partials in fixed order, the last
-//    group finisher sums the ≤16 group rows in fixed order and then, by mode,
-//      TAIL_FEEDBACK  writes the (d+2) feedback (N GPUs over RCCL: all-reduce → glm_update),
-//      TAIL_UPDATE    (1 GPU) evaluates TerminateOnMaxIterOrTol, applies w -= lr/Σw·g plus
-//                     elastic-net regularisation and advances the device round state,
-//      TAIL_XGMI      (N GPUs) exchanges the feedback with every peer over xGMI (xgmi.h: one
+//  * glm_round_kernel: ONE pass over the minibatch rows in HBM. A wave owns a row at a time; each
+//    lane owns a fixed set of EPC-element chunks (16-byte loads), so the coefficient slice AND the
+//    gradient accumulator for those columns live in that lane's registers for the whole kernel
+//    (process): the row is read exactly once, dot → wave sum → loss/multiplier → axpy. Labels and
+//    weights come 64 rows at a time, one per lane (load_labels).
+//  * Two row paths bring the rows in:
+//      register loop (0)    16-byte register loads, U rows per step, two steps in flight. Every
+//                           shape and layout; the only path for MALL-resident data.
+//      loader (LOADER, −1)  bf16 rows of d 513–1024, non-temporal (streamed) batches on at most one
+//                           block per CU: a ninth wave per block streams the rows through an LDS
+//                           ring by LDS-DMA, the 8 consumer waves do the math.
+//  * The waves of a block combine their slices through LDS into one row [grad(d) | Σweight | Σloss]
+//    (the kernel's epilogue), and the round's reduction is fused into the same launch. Four
+//    tails, by GlmTail:
+//      TAIL_PARTIALS        the block writes its row to `partials` and the launch ends (split path)
+//      deterministic        each block publishes its row and draws an arrival ticket (agent-scope
+//                           release/acquire, Guideline 16); the last block of every group of 32
+//                           sums the group's rows in fixed order, the last group finisher sums the
+//                           ≤16 group rows in fixed order: bit-reproducible
+//      atomic, ticketed     blocks add their rows into replicas of one accumulator row with
+//                           no-return float atomics and draw a ticket; the last block sums the
+//                           replicas and completes the round
+//      atomic, deferred     no ticket: launch e + 1 completes round e in its prologue, behind its
+//                           first row loads (defer_prologue, defer_prologue_xgmi)
+//    Completing a round means, by mode,
+//      TAIL_FEEDBACK  writing the (d+2) feedback (N GPUs over RCCL: all-reduce → glm_update),
+//      TAIL_UPDATE    (1 GPU) evaluating TerminateOnMaxIterOrTol, applying w -= lr/Σw·g plus
+//                     elastic-net regularisation and advancing the device round state,
+//      TAIL_XGMI      (N GPUs) exchanging the feedback with every peer over xGMI (xgmi.h: one
 //                     record per rank, bounded tag waits, rank-order sum → bit-identical on all
-//                     ranks) and then updates like TAIL_UPDATE.
+//                     ranks) and then updating like TAIL_UPDATE.
 //    So one SGD round is ONE kernel launch on 1 GPU and on N GPUs: no host synchronisation,
-//    no separate reduce kernels, the whole round capturable in a hipGraph.
-//  * Legacy split path (glm_reduce_stage1 → glm_reduce_update / glm_reduce) kept for the FTRL
-//    local-gradient call and A/B measurements.
-//  * Device round state (int32[8]): [0] round e, [1..2] running flag ping-pong
-//    (running[e&1] gates round e), [3] arrival ticket, [4] rounds executed.
+//    no separate reduce kernels, the whole round capturable in a hipGraph. LR, SVC, LinReg and the
+//    FTRL local gradient all run through fmlx_glm_round.
+//  * glm_round_wide_kernel: rows wider than one wave's registers, a block's 8 waves split the columns.
+//  * Split path (fmlx_glm_grad_partials → fmlx_glm_reduce_update, or an all-reduce → fmlx_glm_update):
+//    three launches per round, kept as the fused round's yardstick. Its users are
+//    tests/test_glm_gpu.py::test_grad_partials_match_torch and the "3-launch" config of
+//    scripts/bench_glm_kernel.py.
+//  * Device round state (int32[8], glm_core.h): [ST_ROUND] round e, [ST_RUN0..+1] running flag
+//    ping-pong (running[e&1] gates round e), [ST_ARRIVE] arrival counter of the split path,
+//    [ST_EXECUTED] rounds executed. Deferred mode: consecutive launches read their round number
+//    alternately from [ST_ROUND] and [ST_ROUND_ALT] (launch e publishes e + 1 into the word launch
+//    e + 1 reads, so no block of launch e can observe it), and [ST_DONE] ends the iteration in place
+//    of the running flags.
 //    The batch of round e is rows [(e mod P)·B, min(+B, n)), P = ceil(n/B): exactly the
 //    reference's sequential slicing with reset-to-0 (SGD.java:263-268).
 #include "common.h"
@@ -66,7 +88,7 @@ struct GlmTail {
   int parity;      // deferred: this launch reads its round number from state[parity ? ALT : ROUND]
   void* cw;        // deferred: [2][d] coefficients of the last two rounds
   int wl_off;      // deferred: byte offset of the block's [d] coefficient image in LDS
-  int ring_off;    // LDS-DMA row path: byte offset of the [WPB][DEPTH][U][2 KiB] row ring
+  int ring_off;    // loader row path: byte offset of its [LOADER_SLOTS][16 KiB] row ring in LDS
   int xb_off;      // deferred TAIL_XGMI: byte offset of the lead block's [d+2] exchange row in LDS
   long long* trace;  // diagnostics (null = off): per block {start, rows done, end, hw id} in
                      // 100 MHz s_memrealtime ticks (scripts/trace_glm_blocks.py)
@@ -428,17 +450,6 @@ __device__ bool defer_prologue_xgmi(const GlmTail& tl, A* coef, int* state, int 
 // ------------------------------------------------------------------------------------------
 // K4/K5/K6 — fused minibatch loss + gradient partials
 // ------------------------------------------------------------------------------------------
-// Sum over aligned segments of L lanes (L = 8 or 16) with DPP; every lane of a segment gets the
-// segment's total. Quad xor1 / xor2 → row_half_mirror (8) → row_mirror (16).
-template <int L>
-__device__ __forceinline__ float seg_sum_dpp(float v) {
-  v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
-  v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
-  v += dpp_mov<0x141>(v);  // row_half_mirror: quads of an 8-lane half swap
-  if constexpr (L == 16) v += dpp_mov<0x140>(v);  // row_mirror: 8-lane halves of a row swap
-  return v;
-}
-
 // register-light shapes are capped at 128 VGPRs (4 waves per SIMD) so that two 8-wave blocks
 // share a CU (the 512-block grids); everything else keeps the compiler's choice and runs one
 // block per CU — under the 128 cap the row loop spills to scratch, and every spill reload is a
@@ -472,9 +483,9 @@ __device__ __forceinline__ void dma16_nt(const void* g, unsigned lds) {
 // per-XCD L2 accumulator replicas, and a tail prefetch of the next round's rows; all exact, all
 // slower: profiles/r3/lr_{dyn_schedule,pair_schedule,l2acc,tail_prefetch_timegated}_ab_1gpu.jsonl.)
 //
-// DEPTH selects the row path: 0 = the register loop above, 2–4 = a per-wave LDS-DMA ring of DEPTH
-// steps, LOADER (−1) = WPB consumer waves plus one loader wave that streams the block's rows
-// through a ring of LOADER_SLOTS 16-KiB slots (see the path's own comment).
+// DEPTH selects the row path: 0 = the register loop above, LOADER (−1) = WPB consumer waves plus
+// one loader wave that streams the block's rows through a ring of LOADER_SLOTS 16-KiB slots (see
+// the path's own comment).
 constexpr int LOADER = -1;
 constexpr int LOADER_SLOTS = 4;
 constexpr int LOADER_SLOT_BYTES = 16384;  // 8 rows × 2 KiB
@@ -679,78 +690,7 @@ __global__ __launch_bounds__((WPB + (DEPTH < 0 ? 1 : 0)) * 64, (DEPTH < 0 ? 1 : 
       }
     }
   };
-  if constexpr (DEPTH > 0) {
-    // ---- LDS-DMA row path (bf16 rows of 65–128 16-byte chunks). Each wave owns a ring of DEPTH
-    // steps × U rows × 2 KiB in LDS; row loads are global_load_lds_dwordx4 … nt (two per row:
-    // chunks lane and lane + 64), so DEPTH − 1 steps stay in flight through the math whatever
-    // the registers hold, and the loads never write VGPRs (the streaming probe: 31.7 µs per 200 MB
-    // batch vs 33.3 for 16-byte register loads, profiles/r4/lr_probe_lds.log). A step's rows are
-    // read back with ds_read_b128 into the same per-lane chunk layout the register path uses.
-    static_assert(sizeof(T) == 2 && EPC == 8 && CPL == 2, "LDS-DMA ring: bf16 rows of 65-128 chunks");
-    extern __shared__ __align__(16) unsigned char smem_r[];
-    typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) u32x4_t lds_u4_t;
-    unsigned char* ring_w = smem_r + tl.ring_off + (long)wave * (DEPTH * U * 2048);
-    const unsigned ring_a = __builtin_amdgcn_readfirstlane((unsigned)(size_t)ring_w);
-    const long nrw = r_first < end ? (end - r_first + W - 1) / W : 0;  // rows of this wave
-    const long nst = (nrw + U - 1) / U;                                 // steps of this wave
-    const int c1 = lane + 64 < nch ? lane + 64 : nch - 1;
-    auto issue = [&](long t) {
-      const unsigned base = ring_a + (unsigned)((t % DEPTH) * U) * 2048u;
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        long ru = r_first + (t * U + u) * W;
-        ru = ru < end ? ru : r_first;  // past the wave's rows: a valid row again, masked below
-        const T* row = X + ru * ld;
-        dma16_nt(row + lane * EPC, base + u * 2048u);
-        dma16_nt(row + c1 * EPC, base + u * 2048u + 1024u);
-      }
-    };
-    auto read = [&](long t, Chunk<T, EPC> (&x)[U][CPL], A (&yy)[U], A (&ww)[U], bool (&vv)[U]) {
-      const long j0 = t * U;
-      if ((j0 & 63) == 0 && j0 > 0) load_labels(j0);
-      const unsigned char* sl = ring_w + (t % DEPTH) * U * 2048;
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-#pragma unroll
-        for (int k = 0; k < CPL; ++k) {
-          const u32x4_t v = *(const lds_u4_t*)(sl + u * 2048 + k * 1024 + lane * 16);
-          __builtin_memcpy(x[u][k].v, &v, 16);
-        }
-        vv[u] = j0 + u < nrw;
-        yy[u] = lane_val(ylab, (int)((j0 + u) & 63));
-        ww[u] = lane_val(wlab, (int)((j0 + u) & 63));
-      }
-    };
-    if (nst > 0) {
-      load_labels(0);
-#pragma unroll
-      for (int t = 0; t < DEPTH - 1; ++t)
-        if (t < nst) issue(t);
-    }
-    if (tl.defer && (tl.mode == TAIL_XGMI ? defer_prologue_xgmi<A>(tl, coef, state, e, d, wdef)
-                                          : defer_prologue<A>(tl, coef, state, e, d, wdef))) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA may land after the wave exits
-      return;
-    }
-    if (nst > 0) {
-      load_w();
-      for (long t = 0; t < nst; ++t) {
-        // step t + DEPTH − 1 goes into the slot step t − 1 was read from (its ds_reads are done:
-        // their values fed step t − 1's math)
-        if (t + DEPTH - 1 < nst) {
-          issue(t + DEPTH - 1);
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * U * (DEPTH - 1)) : "memory");  // step t landed
-        } else {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        read(t, xa, ya, wa, va);
-        process(xa, ya, wa, va);
-      }
-    }
-    // the epilogue's LDS buffers alias the ring: every wave of the block is past its last read
-    __syncthreads();
-  } else if constexpr (DEPTH < 0) {
+  if constexpr (DEPTH < 0) {
     // ---- Loader/consumer row path (bf16 rows of 65–128 16-byte chunks, U = 1). The block is WPB
     // consumer waves plus one loader wave (wave WPB). Consumer wave q still owns rows
     // start + b·WPB + q + j·W, j ascending, so labels, row census and per-wave accumulation order
@@ -1123,16 +1063,6 @@ __global__ __launch_bounds__(256) void glm_reduce_update_kernel(
 }
 
 template <typename A>
-__global__ __launch_bounds__(256) void glm_reduce_kernel(const A* __restrict__ stage1, int ngroups, int d,
-                                                         A* __restrict__ feedback, const int* __restrict__ state) {
-  int e;
-  if (!round_running(state, e)) return;
-  const long stride = d + 2;
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c < stride) feedback[c] = sum_groups(stage1, ngroups, stride, c);
-}
-
-template <typename A>
 __global__ __launch_bounds__(256) void glm_update_kernel(const A* __restrict__ feedback, int d, A* __restrict__ coef,
                                                          int* __restrict__ state, int max_iter, A tol, A lr, A reg,
                                                          A en) {
@@ -1359,95 +1289,95 @@ static int g_ticket2 = 0;   // two-level tickets (A/B knob)
 static long long* g_trace = nullptr;  // per-block timestamps of the next launches (diagnostics)
 
 // row path of the fused round: −1 = automatic (the loader/consumer path where it applies, else
-// register loads), 0 = 16-byte register loads, 2–4 = per-wave LDS-DMA ring of that many steps
-static int g_dma_depth = -1;
-static int g_row_path = 0;  // row path of the last fused-round launch (−1 loader, 0 registers, 2–4 ring)
+// register loads), 0 = 16-byte register loads
+static int g_row_select = -1;
+static int g_row_path = 0;  // row path of the last fused-round launch (−1 loader, 0 registers)
 
-template <typename T, int EPC, int CPL, int U, int DEPTH>
-int launch_grad_k(const void* X, long ld, const void* y, const void* wt, void* coef, long n, int d, long B, int loss,
-                  int* state, void* partials, int nblocks, GlmTail t2, bool nt, hipStream_t s) {
+// what every layer of the fused round's dispatch passes on unchanged
+struct RoundArgs {
+  const void* X;
+  long ld;
+  const void *y, *wt;
+  void* coef;
+  long n;
+  int d;
+  long B;
+  int loss;
+  int* state;
+  void* partials;
+  int nblocks;
+};
+
+template <typename T, int EPC, int CPL, int U, int PATH>
+int launch_grad_k(const RoundArgs& a, GlmTail t2, bool nt, hipStream_t s) {
   typedef typename AccOf<T>::type A;
-  // epilogue LDS: [WPB or WPB/2][d] wave rows | [WPB][2] | ticket flag; the DMA ring (if any)
+  // epilogue LDS: [WPB or WPB/2][d] wave rows | [WPB][2] | ticket flag; the loader path's row ring
   // starts at 0 and the epilogue buffers alias it; the deferred mode's w image follows both
-  const size_t tail = (size_t)(t2.flat_lds ? WPB : WPB / 2) * d * sizeof(A) + WPB * 2 * sizeof(A) + 16;
-  const size_t ring = DEPTH < 0 ? (size_t)LOADER_SLOTS * LOADER_SLOT_BYTES : (size_t)WPB * DEPTH * U * 2048;
-  constexpr int NW = WPB + (DEPTH < 0 ? 1 : 0);  // the loader path adds its loader wave
+  const size_t tail = (size_t)(t2.flat_lds ? WPB : WPB / 2) * a.d * sizeof(A) + WPB * 2 * sizeof(A) + 16;
+  const size_t ring = PATH == LOADER ? (size_t)LOADER_SLOTS * LOADER_SLOT_BYTES : 0;
+  constexpr int NW = WPB + (PATH == LOADER ? 1 : 0);  // the loader path adds its loader wave
   size_t shmem = tail > ring ? tail : ring;
   t2.ring_off = 0;
   if (t2.defer) {
     t2.wl_off = (int)((shmem + 15) & ~(size_t)15);
-    shmem = (size_t)t2.wl_off + (size_t)d * sizeof(A);
+    shmem = (size_t)t2.wl_off + (size_t)a.d * sizeof(A);
     if (t2.mode == TAIL_XGMI) {  // the lead block's exchange row (never aliased with the ring)
       t2.xb_off = (int)((shmem + 15) & ~(size_t)15);
-      shmem = (size_t)t2.xb_off + (size_t)(d + 2) * sizeof(A);
+      shmem = (size_t)t2.xb_off + (size_t)(a.d + 2) * sizeof(A);
     }
   }
   if (g_lds_pad >= 0) {
     shmem += (size_t)g_lds_pad;
   } else {
-    const long per_cu = (nblocks + NUM_CU - 1) / NUM_CU;
+    const long per_cu = (a.nblocks + NUM_CU - 1) / NUM_CU;
     if (per_cu <= 3) {
       const size_t want = (size_t)(LDS_PER_CU / (per_cu + 1) + 1024);
       if (shmem < want) shmem = want;
     }
   }
   if (shmem > (size_t)LDS_PER_CU) return -8;
-  if constexpr (EPC * sizeof(T) == 16 && sizeof(T) == 2) {
-    if (nt) {
-      hipLaunchKernelGGL((glm_round_kernel<T, EPC, CPL, U, WPB, true, DEPTH>), dim3(nblocks), dim3(NW * 64), shmem, s,
-                         (const T*)X, ld, (const A*)y, (const A*)wt, (A*)coef, n, d, B, loss, state, (A*)partials, t2);
-      return (int)hipGetLastError();
-    }
-  }
-  if constexpr (DEPTH == 0) {
-    hipLaunchKernelGGL((glm_round_kernel<T, EPC, CPL, U, WPB, false>), dim3(nblocks), dim3(WPB * 64), shmem, s,
-                       (const T*)X, ld, (const A*)y, (const A*)wt, (A*)coef, n, d, B, loss, state, (A*)partials, t2);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(a.nblocks), dim3(NW * 64), shmem, s, (const T*)a.X, a.ld, (const A*)a.y,
+                       (const A*)a.wt, (A*)a.coef, a.n, a.d, a.B, a.loss, a.state, (A*)a.partials, t2);
     return (int)hipGetLastError();
+  };
+  if constexpr (EPC * sizeof(T) == 16 && sizeof(T) == 2) {
+    if (nt) return launch(glm_round_kernel<T, EPC, CPL, U, WPB, true, PATH>);
   }
+  if constexpr (PATH == 0) return launch(glm_round_kernel<T, EPC, CPL, U, WPB, false>);
   return -9;
 }
 
 template <typename T, int EPC, int CPL, int U>
-int launch_grad_u(const void* X, long ld, const void* y, const void* wt, void* coef, long n, int d, long B, int loss,
-                  int* state, void* partials, int nblocks, const GlmTail& tl, int flags, hipStream_t s) {
+int launch_grad_u(const RoundArgs& a, const GlmTail& tl, int flags, hipStream_t s) {
   typedef typename AccOf<T>::type A;
   GlmTail t2 = tl;
-  t2.nbatch = (n > 0 && B > 0) ? (int)((n + B - 1) / B) : 0;
-  t2.flat_lds = tl.mode != TAIL_PARTIALS && !tl.det && (size_t)WPB * d * sizeof(A) <= 64 * 1024;
+  t2.nbatch = (a.n > 0 && a.B > 0) ? (int)((a.n + a.B - 1) / a.B) : 0;
+  t2.flat_lds = tl.mode != TAIL_PARTIALS && !tl.det && (size_t)WPB * a.d * sizeof(A) <= 64 * 1024;
   // the deferred prologue needs the flat atomic tail
   if (t2.defer && (!t2.flat_lds || (tl.mode != TAIL_UPDATE && tl.mode != TAIL_XGMI) || tl.det || tl.cw == nullptr))
     return -7;
   const bool nt = g_nt >= 0 ? g_nt != 0 : (flags & 1) != 0;
-  // LDS-DMA ring: bf16 rows of 65–128 16-byte chunks (d 513–1024), 16-byte aligned, non-temporal
 #ifndef FMLX_ISA_PROBE_U
   if constexpr (sizeof(T) == 2 && EPC == 8 && CPL == 2) {
     // automatic: the loader/consumer path for streamed (non-temporal) batches on at most one
     // block per CU, when its LDS fits (launch_grad_k answers −8 before launching if it does not).
     // 36.6–36.9 vs 38.4–38.5 µs per round, profiles/r7/lr_loader_ab_1gpu.jsonl. MALL-resident data
     // (default-policy loads) keeps the register loop: the path was only measured with nt fills.
-    if (g_dma_depth < 0 && nt && nblocks <= NUM_CU) {
-      const int rc = launch_grad_k<T, EPC, CPL, 1, LOADER>(X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, t2, nt, s);
+    if (g_row_select < 0 && nt && a.nblocks <= NUM_CU) {
+      const int rc = launch_grad_k<T, EPC, CPL, 1, LOADER>(a, t2, nt, s);
       g_row_path = LOADER;
       if (rc != -8) return rc;
-    }
-    if (g_dma_depth > 0 && nt) {
-      g_row_path = g_dma_depth < 4 ? g_dma_depth : 4;
-      switch (g_dma_depth) {
-        case 2: return launch_grad_k<T, EPC, CPL, U, 2>(X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, t2, nt, s);
-        case 3: return launch_grad_k<T, EPC, CPL, U, 3>(X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, t2, nt, s);
-        default: return launch_grad_k<T, EPC, CPL, U, 4>(X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, t2, nt, s);
-      }
     }
   }
 #endif
   g_row_path = 0;
-  return launch_grad_k<T, EPC, CPL, U, 0>(X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, t2, nt, s);
+  return launch_grad_k<T, EPC, CPL, U, 0>(a, t2, nt, s);
 }
 
 // rows in flight per wave = 2·U (software pipeline); u == 0 picks the default for the shape
 template <typename T, int EPC, int CPL>
-int launch_grad(int u, const void* X, long ld, const void* y, const void* wt, void* coef, long n, int d, long B,
-                int loss, int* state, void* partials, int nblocks, const GlmTail& tl, int flags, hipStream_t s) {
+int launch_grad(int u, const RoundArgs& a, const GlmTail& tl, int flags, hipStream_t s) {
   constexpr int BYTES = CPL * EPC * (int)sizeof(T);
   // default: 4 rows in flight per wave (U = 2) up to 32 bytes per lane, 2 above. Flagship
   // 1000 × bf16 (32 bytes per lane) with the deferred tail, round 3: U=2 on 256 blocks 38.97 µs
@@ -1455,77 +1385,88 @@ int launch_grad(int u, const void* X, long ld, const void* y, const void* wt, vo
   // deferred tail, had measured U=1 faster: 37.9 vs 39.1 µs)
   if (u <= 0) u = BYTES <= 32 ? 2 : 1;
 #ifdef FMLX_ISA_PROBE_U  // one row-loop variant only (ISA inspection)
-  return launch_grad_u<T, EPC, CPL, FMLX_ISA_PROBE_U>(X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, tl, flags, s);
+  return launch_grad_u<T, EPC, CPL, FMLX_ISA_PROBE_U>(a, tl, flags, s);
 #endif
-  // (compile-time guards: the multi-row variants of wide rows would only exist to spill)
+  // (compile-time guard: the multi-row variants of wide rows would only exist to spill)
   if constexpr (BYTES <= 32) {
-    if (u >= 4)
-      return launch_grad_u<T, EPC, CPL, 4>(X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, tl, flags, s);
+    if (u >= 4) return launch_grad_u<T, EPC, CPL, 4>(a, tl, flags, s);
+    if (u >= 2) return launch_grad_u<T, EPC, CPL, 2>(a, tl, flags, s);
   }
-  if constexpr (BYTES <= 32) {
-    if (u >= 2)
-      return launch_grad_u<T, EPC, CPL, 2>(X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, tl, flags, s);
-  }
-  return launch_grad_u<T, EPC, CPL, 1>(X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, tl, flags, s);
+  return launch_grad_u<T, EPC, CPL, 1>(a, tl, flags, s);
 }
 
 #ifndef FMLX_ISA_PROBE
-template <typename T, int EPC>
-int launch_grad_cpl(int cpl, int u, const void* X, long ld, const void* y, const void* wt, void* coef, long n, int d,
-                    long B, int loss, int* state, void* partials, int nblocks, const GlmTail& tl, int flags,
-                    hipStream_t s) {
+// The one map from the host's (dtype, epc, cpl) to <T, EPC, CPL>: epc = elements per 16/8/4/2-byte
+// chunk, chosen by the host so that d % epc == 0 and rows are aligned; cpl = chunks per lane (power
+// of two, 64·cpl·epc >= d). f is called with a Layout tag and its result returned; −1 for a
+// triple outside the sets below. A caller that ships fewer layouts filters with `if constexpr`
+// on the tag, so nothing else is instantiated.
+template <typename T_, int EPC_, int CPL_>
+struct Layout {
+  typedef T_ T;
+  static constexpr int EPC = EPC_, CPL = CPL_;
+};
+template <typename T, int EPC, typename F>
+int with_cpl(int cpl, F&& f) {
   switch (cpl) {
-    case 1: return launch_grad<T, EPC, 1>(u, X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, tl, flags, s);
-    case 2: return launch_grad<T, EPC, 2>(u, X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, tl, flags, s);
-    case 4: return launch_grad<T, EPC, 4>(u, X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, tl, flags, s);
-    case 8: return launch_grad<T, EPC, 8>(u, X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, tl, flags, s);
+    case 1: return f(Layout<T, EPC, 1>{});
+    case 2: return f(Layout<T, EPC, 2>{});
+    case 4: return f(Layout<T, EPC, 4>{});
+    case 8: return f(Layout<T, EPC, 8>{});
   }
   return -1;
 }
-
-int launch_round(int dtype, int epc, int cpl, int u, const void* X, long ld, const void* y, const void* wt, void* coef,
-                 long n, int d, long B, int loss, int* state, void* partials, int nblocks, const GlmTail& tl, int flags,
-                 hipStream_t s) {
+template <typename F>
+int with_layout(int dtype, int epc, int cpl, F&& f) {
   if (dtype == DT_BF16) {
-    if (epc == 8) return launch_grad_cpl<bf16_t, 8>(cpl, u, X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, tl, flags, s);
-    if (epc == 4) return launch_grad_cpl<bf16_t, 4>(cpl, u, X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, tl, flags, s);
-    if (epc == 2) return launch_grad_cpl<bf16_t, 2>(cpl, u, X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, tl, flags, s);
-    if (epc == 1) return launch_grad_cpl<bf16_t, 1>(cpl, u, X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, tl, flags, s);
+    if (epc == 8) return with_cpl<bf16_t, 8>(cpl, f);
+    if (epc == 4) return with_cpl<bf16_t, 4>(cpl, f);
+    if (epc == 2) return with_cpl<bf16_t, 2>(cpl, f);
+    if (epc == 1) return with_cpl<bf16_t, 1>(cpl, f);
   } else if (dtype == DT_F32) {
-    if (epc == 4) return launch_grad_cpl<float, 4>(cpl, u, X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, tl, flags, s);
-    if (epc == 2) return launch_grad_cpl<float, 2>(cpl, u, X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, tl, flags, s);
-    if (epc == 1) return launch_grad_cpl<float, 1>(cpl, u, X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, tl, flags, s);
+    if (epc == 4) return with_cpl<float, 4>(cpl, f);
+    if (epc == 2) return with_cpl<float, 2>(cpl, f);
+    if (epc == 1) return with_cpl<float, 1>(cpl, f);
   } else if (dtype == DT_F64) {
-    if (epc == 2) return launch_grad_cpl<double, 2>(cpl, u, X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, tl, flags, s);
-    if (epc == 1) return launch_grad_cpl<double, 1>(cpl, u, X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, tl, flags, s);
+    if (epc == 2) return with_cpl<double, 2>(cpl, f);
+    if (epc == 1) return with_cpl<double, 1>(cpl, f);
   }
   return -1;
 }
 
-template <typename T, int EPC, int CPL>
-int launch_pred(const void* X, long ld, long n, int d, const void* coef, int mode, double thr, double* pred,
-                double* raw, hipStream_t s) {
-  long waves = n;
-  int blocks = (int)((waves + 3) / 4);
-  if (blocks > 4096) blocks = 4096;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL((glm_predict_kernel<T, EPC, CPL>), dim3(blocks), dim3(256), 0, s, (const T*)X, ld, n, d,
-                     (const typename AccOf<T>::type*)coef, mode, thr, pred, raw);
-  return (int)hipGetLastError();
+int launch_round(int dtype, int epc, int cpl, int u, const RoundArgs& a, const GlmTail& tl, int flags, hipStream_t s) {
+  return with_layout(dtype, epc, cpl, [&](auto l) {
+    typedef decltype(l) L;
+    return launch_grad<typename L::T, L::EPC, L::CPL>(u, a, tl, flags, s);
+  });
 }
 
-template <typename T, int EPC>
-int launch_pred_cpl(int cpl, const void* X, long ld, long n, int d, const void* coef, int mode, double thr,
-                    double* pred, double* raw, hipStream_t s) {
-  switch (cpl) {
-    case 1: return launch_pred<T, EPC, 1>(X, ld, n, d, coef, mode, thr, pred, raw, s);
-    case 2: return launch_pred<T, EPC, 2>(X, ld, n, d, coef, mode, thr, pred, raw, s);
-    case 4: return launch_pred<T, EPC, 4>(X, ld, n, d, coef, mode, thr, pred, raw, s);
-    case 8: return launch_pred<T, EPC, 8>(X, ld, n, d, coef, mode, thr, pred, raw, s);
-  }
-  return -1;
+// the GlmTail fields both round entry points fill
+GlmTail make_tail(int mode, int det, int* cnt, void* acc, void* stage1, void* feedback, int d, int max_iter, double tol,
+                  double lr, double reg, double en) {
+  GlmTail tl{};
+  tl.mode = mode;
+  tl.max_iter = max_iter;
+  tl.det = det;
+  tl.cnt = cnt;
+  tl.acc = acc;
+  tl.acc_reps = g_acc_reps;
+  tl.acc_ld = ((long)d + 2 + 63) / 64 * 64;
+  tl.ticket2 = g_ticket2;
+  tl.stage1 = stage1;
+  tl.feedback = feedback;
+  tl.tol = tol;
+  tl.lr = lr;
+  tl.reg = reg;
+  tl.en = en;
+  return tl;
 }
 
+// the split path's accumulator type: f is called with a value of it
+template <typename F>
+int with_acc(int acc_f64, F&& f) {
+  return acc_f64 ? f(double{}) : f(float{});
+}
 #endif  // FMLX_ISA_PROBE
 }  // namespace
 
@@ -1535,12 +1476,10 @@ int launch_pred_cpl(int cpl, const void* X, long ld, long n, int d, const void* 
 // library never holds this function, so it is not one of its entry points)
 extern "C" int fmlx_glm_isa_probe(int u, const void* X, long ld, const void* y, void* coef, int* state,
                                   const GlmTail* tl) {
-  return launch_grad<bf16_t, 8, 2>(u, X, ld, y, nullptr, coef, 1, 1000, 1, 0, state, nullptr, 224, *tl, 1, 0);
+  return launch_grad<bf16_t, 8, 2>(u, RoundArgs{X, ld, y, nullptr, coef, 1, 1000, 1, 0, state, nullptr, 224}, *tl, 1, 0);
 }
 #else
 
-// epc = elements per 16/8/4/2-byte chunk chosen by the host so that d % epc == 0 and rows are
-// aligned; cpl = chunks per lane (power of two, 64*cpl*epc >= d).
 FMLX_API int fmlx_glm_set_tuning(long lds_pad, int nt) {
   g_lds_pad = lds_pad;
   g_nt = nt;
@@ -1557,10 +1496,10 @@ FMLX_API void fmlx_glm_set_trace(void* trace) {
 FMLX_API int fmlx_glm_cnt_elems() { return 128; }
 
 // Row path of the fused round (bf16 rows of d 513–1024): −1 = automatic (loader/consumer path
-// for streamed batches), 0 = register loads, 2–4 = per-wave LDS-DMA ring of that many steps
-FMLX_API int fmlx_glm_set_dma(int depth) {
-  if (depth < -1 || depth > 4 || depth == 1) return -1;
-  g_dma_depth = depth;
+// for streamed batches), 0 = register loads
+FMLX_API int fmlx_glm_set_dma(int path) {
+  if (path != -1 && path != 0) return -1;
+  g_row_select = path;
   return 0;
 }
 
@@ -1583,8 +1522,8 @@ FMLX_API int fmlx_glm_grad_partials(int dtype, int epc, int cpl, int u, const vo
                                     void* partials, int nblocks, void* stream) {
   GlmTail tl{};
   tl.mode = TAIL_PARTIALS;
-  return launch_round(dtype, epc, cpl, u, X, ld, y, wt, const_cast<void*>(coef), n, d, B, loss,
-                      const_cast<int*>(state), partials, nblocks, tl, 0, (hipStream_t)stream);
+  const RoundArgs a{X, ld, y, wt, const_cast<void*>(coef), n, d, B, loss, const_cast<int*>(state), partials, nblocks};
+  return launch_round(dtype, epc, cpl, u, a, tl, 0, (hipStream_t)stream);
 }
 
 // One whole SGD round in one launch (see the header comment). cnt: int32[17] zero-initialised;
@@ -1602,58 +1541,20 @@ FMLX_API int fmlx_glm_round(int dtype, int epc, int cpl, int u, const void* X, l
   if (mode != TAIL_PARTIALS && !det && (nblocks > TAIL_GROUP * TAIL_TOP || acc == nullptr)) return -4;
   if (mode == TAIL_FEEDBACK && feedback == nullptr) return -5;
   if (mode == TAIL_XGMI && (d + 2 > xgmi::GLM_MAX || peers == nullptr || world > xgmi::MAX_RANKS)) return -6;
-  GlmTail tl{};
-  tl.mode = mode;
-  tl.max_iter = max_iter;
-  tl.det = det;
-  tl.cnt = cnt;
-  tl.acc = acc;
-  tl.acc_reps = g_acc_reps;
-  tl.acc_ld = ((long)d + 2 + 63) / 64 * 64;
-  tl.ticket2 = g_ticket2;
-  tl.stage1 = stage1;
-  tl.feedback = feedback;
-  tl.tol = tol;
-  tl.lr = lr;
-  tl.reg = reg;
-  tl.en = en;
+  GlmTail tl = make_tail(mode, det, cnt, acc, stage1, feedback, d, max_iter, tol, lr, reg, en);
   tl.x = xgmi::Ctx{peers, world, rank, gen, err, spin_limit};
   tl.defer = defer;
   tl.cw = cw;
   tl.trace = g_trace;
+  const RoundArgs a{X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks};
   // `rounds` consecutive rounds, one launch each (a kernel boundary, ~1.5 µs, is cheaper than an
   // in-kernel grid-wide round barrier: measured, scripts/stream_probe2.hip)
   for (int i = 0; i < (rounds > 0 ? rounds : 1); ++i) {
     tl.parity = (parity + i) & 1;  // deferred mode: launches alternate their round-number word
-    const int rc = launch_round(dtype, epc, cpl, u, X, ld, y, wt, coef, n, d, B, loss, state, partials, nblocks, tl,
-                                flags, (hipStream_t)stream);
+    const int rc = launch_round(dtype, epc, cpl, u, a, tl, flags, (hipStream_t)stream);
     if (rc) return rc;
   }
   return 0;
-}
-
-template <typename T, int EPC, int CPL>
-static int launch_wide(const void* X, long ld, const void* y, const void* wt, void* coef, long n, int d, long B,
-                       int loss, int* state, int nblocks, const GlmTail& tl, hipStream_t s) {
-  typedef typename AccOf<T>::type A;
-  const size_t lds = (size_t)(d + 2) * sizeof(A) + 16;
-  if (lds > (size_t)LDS_PER_CU) return -8;
-  hipLaunchKernelGGL((glm_round_wide_kernel<T, EPC, CPL, CPL >= 8 ? 1 : 2>), dim3(nblocks), dim3(WIDE_WAVES * 64), lds,
-                     s, (const T*)X,
-                     ld, (const A*)y, (const A*)wt, (A*)coef, n, d, B, loss, state, tl);
-  return (int)hipGetLastError();
-}
-
-template <typename T, int EPC>
-static int launch_wide_cpl(int cpl, const void* X, long ld, const void* y, const void* wt, void* coef, long n, int d,
-                           long B, int loss, int* state, int nblocks, const GlmTail& tl, hipStream_t s) {
-  switch (cpl) {
-    case 1: return launch_wide<T, EPC, 1>(X, ld, y, wt, coef, n, d, B, loss, state, nblocks, tl, s);
-    case 2: return launch_wide<T, EPC, 2>(X, ld, y, wt, coef, n, d, B, loss, state, nblocks, tl, s);
-    case 4: return launch_wide<T, EPC, 4>(X, ld, y, wt, coef, n, d, B, loss, state, nblocks, tl, s);
-    case 8: return launch_wide<T, EPC, 8>(X, ld, y, wt, coef, n, d, B, loss, state, nblocks, tl, s);
-  }
-  return -1;
 }
 
 // One SGD round on rows too wide for one wave (see glm_round_wide_kernel): 16-byte chunks of EPC
@@ -1667,106 +1568,69 @@ FMLX_API int fmlx_glm_round_wide(int dtype, int epc, int cpl, const void* X, lon
   if (cnt == nullptr || acc == nullptr || nblocks < 1 || nblocks > TAIL_GROUP * TAIL_TOP) return -4;
   if (mode == TAIL_FEEDBACK && feedback == nullptr) return -5;
   if (d % epc != 0 || (d / epc + WIDE_WAVES - 1) / WIDE_WAVES > 64 * cpl) return -6;
-  GlmTail tl{};
-  tl.mode = mode;
-  tl.max_iter = max_iter;
-  tl.cnt = cnt;
-  tl.acc = acc;
-  tl.acc_reps = g_acc_reps;
-  tl.acc_ld = ((long)d + 2 + 63) / 64 * 64;
-  tl.ticket2 = g_ticket2;
-  tl.feedback = feedback;
-  tl.tol = tol;
-  tl.lr = lr;
-  tl.reg = reg;
-  tl.en = en;
+  GlmTail tl = make_tail(mode, 0, cnt, acc, nullptr, feedback, d, max_iter, tol, lr, reg, en);
   tl.nbatch = (n > 0 && B > 0) ? (int)((n + B - 1) / B) : 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == DT_BF16 && epc == 8) return launch_wide_cpl<bf16_t, 8>(cpl, X, ld, y, wt, coef, n, d, B, loss, state, nblocks, tl, s);
-  if (dtype == DT_F32 && epc == 4) return launch_wide_cpl<float, 4>(cpl, X, ld, y, wt, coef, n, d, B, loss, state, nblocks, tl, s);
-  if (dtype == DT_F64 && epc == 2) return launch_wide_cpl<double, 2>(cpl, X, ld, y, wt, coef, n, d, B, loss, state, nblocks, tl, s);
-  return -1;
+  return with_layout(dtype, epc, cpl, [&](auto l) {
+    typedef decltype(l) L;
+    typedef typename L::T T;
+    typedef typename AccOf<T>::type A;
+    if constexpr (L::EPC * sizeof(T) == 16) {  // 16-byte chunks only: bf16/8, fp32/4, fp64/2
+      const size_t lds = (size_t)(d + 2) * sizeof(A) + 16;
+      if (lds > (size_t)LDS_PER_CU) return -8;
+      hipLaunchKernelGGL((glm_round_wide_kernel<T, L::EPC, L::CPL, L::CPL >= 8 ? 1 : 2>), dim3(nblocks),
+                         dim3(WIDE_WAVES * 64), lds, (hipStream_t)stream, (const T*)X, ld, (const A*)y, (const A*)wt,
+                         (A*)coef, n, d, B, loss, state, tl);
+      return (int)hipGetLastError();
+    } else {
+      return -1;
+    }
+  });
 }
 
-// stage1 scratch: [ceil(nparts/16)][d+2] of the accumulator type (nparts <= 512)
-template <typename A>
-static int launch_stage1(const void* partials, int nparts, int d, void* stage1, const int* state, hipStream_t s) {
-  dim3 grid((d + 2 + 255) / 256, (nparts + RED_G - 1) / RED_G);
-  hipLaunchKernelGGL(glm_reduce_stage1_kernel<A>, grid, dim3(256), 0, s, (const A*)partials, nparts, d, (A*)stage1,
-                     state);
-  return (int)hipGetLastError();
-}
-
+// Split path, stages 2 and 3 in one call. stage1 scratch: [ceil(nparts/32)][d+2] of the
+// accumulator type (nparts <= 512)
 FMLX_API int fmlx_glm_reduce_update(int acc_f64, const void* partials, int nparts, int d, void* stage1, void* coef,
                                     void* feedback, int* state, int max_iter, double tol, double lr, double reg,
                                     double en, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const int ngroups = (nparts + RED_G - 1) / RED_G;
   if (ngroups > 16) return -2;
-  int rc = acc_f64 ? launch_stage1<double>(partials, nparts, d, stage1, state, s)
-                   : launch_stage1<float>(partials, nparts, d, stage1, state, s);
-  if (rc) return rc;
-  int blocks = (d + 255) / 256;
-  if (acc_f64)
-    hipLaunchKernelGGL(glm_reduce_update_kernel<double>, dim3(blocks), dim3(256), 0, s, (const double*)stage1,
-                       ngroups, d, (double*)coef, (double*)feedback, state, max_iter, tol, lr, reg, en);
-  else
-    hipLaunchKernelGGL(glm_reduce_update_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)stage1, ngroups,
-                       d, (float*)coef, (float*)feedback, state, max_iter, (float)tol, (float)lr, (float)reg,
-                       (float)en);
-  return (int)hipGetLastError();
-}
-
-FMLX_API int fmlx_glm_reduce(int acc_f64, const void* partials, int nparts, int d, void* stage1, void* feedback,
-                             const int* state, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const int ngroups = (nparts + RED_G - 1) / RED_G;
-  if (ngroups > 16) return -2;
-  int rc = acc_f64 ? launch_stage1<double>(partials, nparts, d, stage1, state, s)
-                   : launch_stage1<float>(partials, nparts, d, stage1, state, s);
-  if (rc) return rc;
-  int blocks = (d + 2 + 255) / 256;
-  if (acc_f64)
-    hipLaunchKernelGGL(glm_reduce_kernel<double>, dim3(blocks), dim3(256), 0, s, (const double*)stage1, ngroups, d,
-                       (double*)feedback, state);
-  else
-    hipLaunchKernelGGL(glm_reduce_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)stage1, ngroups, d,
-                       (float*)feedback, state);
-  return (int)hipGetLastError();
+  return with_acc(acc_f64, [&](auto acc) {
+    typedef decltype(acc) A;
+    hipLaunchKernelGGL(glm_reduce_stage1_kernel<A>, dim3((d + 2 + 255) / 256, ngroups), dim3(256), 0, s,
+                       (const A*)partials, nparts, d, (A*)stage1, state);
+    const int rc = (int)hipGetLastError();
+    if (rc) return rc;
+    hipLaunchKernelGGL(glm_reduce_update_kernel<A>, dim3((d + 255) / 256), dim3(256), 0, s, (const A*)stage1, ngroups,
+                       d, (A*)coef, (A*)feedback, state, max_iter, (A)tol, (A)lr, (A)reg, (A)en);
+    return (int)hipGetLastError();
+  });
 }
 
 FMLX_API int fmlx_glm_update(int acc_f64, const void* feedback, int d, void* coef, int* state, int max_iter,
                              double tol, double lr, double reg, double en, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
   int blocks = (d + 255) / 256;
   if (blocks > 1024) blocks = 1024;
-  if (acc_f64)
-    hipLaunchKernelGGL(glm_update_kernel<double>, dim3(blocks), dim3(256), 0, s, (const double*)feedback, d,
-                       (double*)coef, state, max_iter, tol, lr, reg, en);
-  else
-    hipLaunchKernelGGL(glm_update_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)feedback, d,
-                       (float*)coef, state, max_iter, (float)tol, (float)lr, (float)reg, (float)en);
-  return (int)hipGetLastError();
+  return with_acc(acc_f64, [&](auto acc) {
+    typedef decltype(acc) A;
+    hipLaunchKernelGGL(glm_update_kernel<A>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const A*)feedback, d,
+                       (A*)coef, state, max_iter, (A)tol, (A)lr, (A)reg, (A)en);
+    return (int)hipGetLastError();
+  });
 }
 
 FMLX_API int fmlx_glm_predict(int dtype, int epc, int cpl, const void* X, long ld, long n, int d, const void* coef,
                               int mode, double thr, double* pred, double* raw, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
   if (n == 0) return 0;
-  if (dtype == DT_BF16) {
-    if (epc == 8) return launch_pred_cpl<bf16_t, 8>(cpl, X, ld, n, d, coef, mode, thr, pred, raw, s);
-    if (epc == 4) return launch_pred_cpl<bf16_t, 4>(cpl, X, ld, n, d, coef, mode, thr, pred, raw, s);
-    if (epc == 2) return launch_pred_cpl<bf16_t, 2>(cpl, X, ld, n, d, coef, mode, thr, pred, raw, s);
-    if (epc == 1) return launch_pred_cpl<bf16_t, 1>(cpl, X, ld, n, d, coef, mode, thr, pred, raw, s);
-  } else if (dtype == DT_F32) {
-    if (epc == 4) return launch_pred_cpl<float, 4>(cpl, X, ld, n, d, coef, mode, thr, pred, raw, s);
-    if (epc == 2) return launch_pred_cpl<float, 2>(cpl, X, ld, n, d, coef, mode, thr, pred, raw, s);
-    if (epc == 1) return launch_pred_cpl<float, 1>(cpl, X, ld, n, d, coef, mode, thr, pred, raw, s);
-  } else if (dtype == DT_F64) {
-    if (epc == 2) return launch_pred_cpl<double, 2>(cpl, X, ld, n, d, coef, mode, thr, pred, raw, s);
-    if (epc == 1) return launch_pred_cpl<double, 1>(cpl, X, ld, n, d, coef, mode, thr, pred, raw, s);
-  }
-  return -1;
+  int blocks = (int)((n + 3) / 4);  // one row per wave at a time, 4 waves per block
+  if (blocks > 4096) blocks = 4096;
+  return with_layout(dtype, epc, cpl, [&](auto l) {
+    typedef decltype(l) L;
+    typedef typename L::T T;
+    hipLaunchKernelGGL((glm_predict_kernel<T, L::EPC, L::CPL>), dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                       (const T*)X, ld, n, d, (const typename AccOf<T>::type*)coef, mode, thr, pred, raw);
+    return (int)hipGetLastError();
+  });
 }
 
 #endif  // FMLX_ISA_PROBE

@@ -76,20 +76,23 @@ def set_tail_tuning(acc_reps: int = 4, ticket2: bool = False) -> None:
 #      Streaming probe profiles/r7/lr_probe_loader.log; kernel and driver A/B against
 #      FMLX_GLM_DMA=0 profiles/r7/lr_loader_ab_1gpu.jsonl, lr_bench_loader_ab.log
 #   0  16-byte register loads, two steps of U rows per wave in flight (the round 3–6 kernel)
-# 2–4  per-wave LDS-DMA ring of that many steps (round 4; slower: every wave issues its own DMA
-#      between its own math, profiles/r4/lr_lds_dma_ring_ab_1gpu.jsonl)
+# Any other value is refused at the first use. (Values 2–4 used to select a per-wave LDS-DMA ring of
+# that many steps, round 4. It measured slower — every wave issued its own DMA between its own
+# math, profiles/r4/lr_lds_dma_ring_ab_1gpu.jsonl —, the loader path superseded it, and it was
+# removed in round 8.)
 DMA_DEPTH = int(os.environ.get("FMLX_GLM_DMA", "-1"))
 
 
-def set_dma(depth: int) -> None:
+def set_dma(path: int) -> None:
     """Row path of the fused round: -1 = automatic (loader/consumer path for streamed batches),
-    0 = register loads, 2–4 = per-wave LDS-DMA ring of that many steps."""
-    if native.kernels().fmlx_glm_set_dma(int(depth)) != 0:
-        raise ValueError("depth must be -1, 0, 2, 3 or 4")
+    0 = register loads."""
+    if native.kernels().fmlx_glm_set_dma(int(path)) != 0:
+        raise ValueError("row path (FMLX_GLM_DMA / set_dma) must be -1 (automatic: loader/consumer path for "
+                         "streamed batches) or 0 (register loads), not %r" % (path,))
 
 
 def row_path() -> int:
-    """Row path the last fused-round launch took: -1 loader/consumer, 0 register loads, 2–4 ring."""
+    """Row path the last fused-round launch took: -1 loader/consumer, 0 register loads."""
     return int(native.kernels().fmlx_glm_row_path())
 
 
@@ -299,11 +302,6 @@ def reduce_update(partials, nparts: int, d: int, stage1, coef, feedback, state, 
     native.call("fmlx_glm_reduce_update", int(coef.dtype == torch.float64), native.ptr(partials), nparts, d,
                 native.ptr(stage1), native.ptr(coef), native.ptr(feedback), native.ptr(state), max_iter, tol, lr, reg, en,
                 native.stream_ptr(coef.device))
-
-
-def reduce_only(partials, nparts: int, d: int, stage1, feedback, state) -> None:
-    native.call("fmlx_glm_reduce", int(feedback.dtype == torch.float64), native.ptr(partials), nparts, d,
-                native.ptr(stage1), native.ptr(feedback), native.ptr(state), native.stream_ptr(feedback.device))
 
 
 def update(feedback, d: int, coef, state, max_iter, tol, lr, reg, en) -> None:

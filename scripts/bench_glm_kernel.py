@@ -6,7 +6,7 @@ Variants: ``u`` (rows in flight per wave = 2u), ``b`` (blocks = partial rows), `
 (legacy 3-launch round: grad partials → stage-1 → reduce+update) vs the fused one-launch round,
 ``defer`` (0: ticketed atomic tail; 1: round e − 1 completed in launch e's prologue), ``dma``
 (row path: -1 = automatic, i.e. the loader/consumer path for streamed batches; 0 = register
-loads, the default here; 2–4 = per-wave LDS-DMA ring of that many steps).
+loads, the default here).
 Usage: python scripts/bench_glm_kernel.py --configs "u=2,b=512;u=4,b=256;split=1"
 """
 import argparse

@@ -150,10 +150,14 @@ def test_loader_fit_matches_fp64(loss, defer, d, blocks, B, pitch, monkeypatch):
     assert np.allclose(got, ref, rtol=2e-4, atol=2e-6), np.abs(got - ref).max()
 
 
-@pytest.mark.parametrize("d,blocks,B", [(1000, 8, 1777), (520, 224, N), (1024, 3, 1777)])
-def test_loader_deterministic_tail_bit_identical_to_register_loop(d, blocks, B, monkeypatch):
+@pytest.mark.parametrize("d,blocks,B,weights", [
+    pytest.param(1000, 8, 1777, True, id="1000-8-1777"), pytest.param(520, 224, N, True, id="520-224-%d" % N),
+    pytest.param(1024, 3, 1777, True, id="1024-3-1777"), pytest.param(1000, 3, 61, False, id="1000-3-61-noweights")])
+def test_loader_deterministic_tail_bit_identical_to_register_loop(d, blocks, B, weights, monkeypatch):
     """Fixed-order tail: the loader path twice and the register loop give bit-identical
-    coefficients — same per-row math, same rows in the same order per wave, same tail."""
+    coefficients — same per-row math, same rows in the same order per wave, same tail. The last
+    case has no row weights, a ragged second piece, a ring that wraps many times and batches
+    smaller than one slot."""
     _need_gpu()
     from flink_ml_amd.common.optimizer import SGD
     from flink_ml_amd.ops import glm as gk
@@ -167,7 +171,7 @@ def test_loader_deterministic_tail_bit_identical_to_register_loop(d, blocks, B, 
         for dma in (LOADER, LOADER, 0):
             gk.set_dma(dma)
             sgd = SGD(max_iter=5, learning_rate=0.1, global_batch_size=B, tol=0.0)
-            tr = _trainer(gk, sgd, d, Xd, y, wt, "logistic", blocks)
+            tr = _trainer(gk, sgd, d, Xd, y, wt if weights else None, "logistic", blocks)
             assert tr.scratch.det and not tr.defer
             out.append(tr.fit())
             assert gk.row_path() == dma
@@ -181,10 +185,10 @@ def test_loader_selector_values():
 
     gk.RoundScratch(1, 8, torch.float32, "cuda")  # applies the process default first
     try:
-        for bad in (5, 1):
+        for bad in (5, 1, 3):
             with pytest.raises(ValueError):
                 gk.set_dma(bad)
-        for ok in (0, 3, LOADER):
+        for ok in (0, LOADER):
             gk.set_dma(ok)
     finally:
         gk.set_dma(gk.DMA_DEPTH)
