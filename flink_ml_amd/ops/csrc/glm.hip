@@ -90,10 +90,15 @@ struct GlmTail {
   int wl_off;      // deferred: byte offset of the block's [d] coefficient image in LDS
   int ring_off;    // loader row path: byte offset of its [LOADER_SLOTS][16 KiB] row ring in LDS
   int xb_off;      // deferred TAIL_XGMI: byte offset of the lead block's [d+2] exchange row in LDS
-  long long* trace;  // diagnostics (null = off): per block {start, rows done, end, hw id} in
-                     // 100 MHz s_memrealtime ticks (scripts/trace_glm_blocks.py)
+  long long* trace;  // diagnostics (null = off): per block a record of TRACE_REC stamps in 100 MHz
+                     // s_memrealtime ticks (scripts/trace_glm_blocks.py): {start, rows done, end,
+                     // hw id, prologue done}, then the loader path's {loader past the prologue,
+                     // prefetched step 0, 1, … seen landed}
 };
 constexpr int ACC_MAX_REPS = 8;
+constexpr int TRACE_REC = 16;       // int64 words per block
+constexpr int TRACE_PROLOGUE = 4;   // consumer wave 0, after the prologue's barrier
+constexpr int TRACE_LOADER = 5;     // loader wave past the prologue's barrier, then one per prefetched step
 
 
 // Replaces this rank's feedback fb[0..stride) (in LDS) by the rank-order sum over all ranks.
@@ -344,6 +349,86 @@ __device__ bool defer_prologue(const GlmTail& tl, A* coef, int* state, int e, in
   return stop;
 }
 
+// defer_prologue for the loader/consumer row path: only the block's NT consumer threads (its first
+// NT) take part. The loader wave keeps filling its ring meanwhile — its own sc1 loads would return
+// in order behind its DMA, so inside the prologue it could not issue another fill before the end —
+// and meets the consumers with ONE raw s_barrier at the __syncthreads() below; the stop decision
+// reaches it through the LDS word *stopw, written before that barrier.
+// One memory round trip instead of two: the Σweight/Σloss replicas, the gradient replicas and the
+// previous coefficients are requested together (only sgd_apply needs W, the column loads do not),
+// as glm_round_tail_atomic's one_pass form does. d <= 2·NT on this path (rows of at most 128
+// 16-byte chunks), so a thread owns at most two columns. Replicas are summed in defer_prologue's
+// order: the two give bit-identical w_e.
+template <typename A, int NT>
+__device__ bool defer_prologue_consumers(const GlmTail& tl, A* coef, int* state, int e, int d, A* wl, int* stopw) {
+  const int tid = threadIdx.x;
+  const int R = tl.acc_reps > 1 ? tl.acc_reps : 1;
+  const long ald = tl.acc_ld;
+  const long slot = (long)ACC_MAX_REPS * ald;
+  A* ring = (A*)tl.acc;
+  A* cw = (A*)tl.cw;
+  A* fb = (A*)tl.feedback;
+  const bool lead = blockIdx.x == 0;
+  const long ca = tid, cb = tid + NT;
+  bool stop = false;
+  if (e == 0) {
+    if (ca < d) wl[ca] = coef[ca];
+    if (cb < d) wl[cb] = coef[cb];
+  } else {
+    const A* prev = ring + (long)((e + 2) % 3) * slot;
+    const A* wp = cw + (long)((e - 1) & 1) * d;
+    const long la = ca < d ? ca : 0, lb = cb < d ? cb : 0;
+    A vw[ACC_MAX_REPS], vl[ACC_MAX_REPS], va[ACC_MAX_REPS], vb[ACC_MAX_REPS];
+#pragma unroll
+    for (int q = 0; q < ACC_MAX_REPS; ++q) {
+      vw[q] = q < R ? ld_agent(prev + q * ald + d) : (A)0;
+      vl[q] = q < R ? ld_agent(prev + q * ald + d + 1) : (A)0;
+      va[q] = q < R ? ld_agent(prev + q * ald + la) : (A)0;
+      vb[q] = q < R ? ld_agent(prev + q * ald + lb) : (A)0;
+    }
+    const A wa = wp[la], wb = wp[lb];
+    A W = (A)0, L = (A)0, ga = (A)0, gb = (A)0;
+#pragma unroll
+    for (int q = 0; q < ACC_MAX_REPS; ++q) {
+      W += vw[q];
+      L += vl[q];
+      ga += va[q];
+      gb += vb[q];
+    }
+    stop = !(e < tl.max_iter && L / W > (A)tl.tol);
+    const A lr = (A)tl.lr, reg = (A)tl.reg, en = (A)tl.en;
+    if (ca < d) {
+      wl[ca] = sgd_apply<A>(wa, ga, W, lr, reg, en);
+      if (lead && fb) fb[ca] = ga;
+    }
+    if (cb < d) {
+      wl[cb] = sgd_apply<A>(wb, gb, W, lr, reg, en);
+      if (lead && fb) fb[cb] = gb;
+    }
+    if (lead && fb && tid == 0) {
+      fb[d] = W;
+      fb[d + 1] = L;
+    }
+  }
+  A* nxt = ring + (long)((e + 1) % 3) * slot;
+  for (long i = (long)blockIdx.x * NT + tid; i < slot; i += (long)gridDim.x * NT) nxt[i] = (A)0;
+  if (tid == 0) *stopw = stop ? 1 : 0;
+  __syncthreads();
+  if (lead) {
+    A* wc = cw + (long)(e & 1) * d;
+    for (long c = tid; c < d; c += NT) {
+      wc[c] = wl[c];
+      coef[c] = wl[c];  // launch 0: the value every block just read
+    }
+    if (tid == 0) {
+      state[tl.parity ? ST_ROUND : ST_ROUND_ALT] = e + 1;
+      if (e > 0) state[ST_EXECUTED] += 1;
+      if (stop) state[ST_DONE] = 1;
+    }
+  }
+  return stop;
+}
+
 // Deferred round completion across ranks (TAIL_XGMI with the atomic flat tail; SGD.java:246-255
 // applies round e's update at the start of round e + 1). Launch e's blocks add round e's gradient
 // into this rank's accumulator slot e % 3 and exit — no ticket, no serial last-block tail. Launch
@@ -474,6 +559,19 @@ __device__ __forceinline__ void dma16_nt(const void* g, unsigned lds) {
                : "memory");
 }
 
+// Diagnostics of the loader wave (GlmTail::trace): with NS steps of PIECES loads each issued and
+// nothing after them, t[i] is the time at which step i was seen landed. This drains the prefetch,
+// so a traced launch starts its ring later than an untraced one.
+template <int I, int NS, int PIECES>
+__device__ __forceinline__ void stamp_landed(long long (&t)[NS]) {
+  if constexpr (I < NS) {
+    constexpr int left = PIECES * (NS - 1 - I);
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(left < 63 ? left : 63) : "memory");
+    t[I] = (long long)__builtin_amdgcn_s_memrealtime();
+    stamp_landed<I + 1, NS, PIECES>(t);
+  }
+}
+
 // X / y / wt are deliberately NOT __restrict__: with restrict the compiler may move the row
 // prefetch loads below the compiler fence that pins them ahead of the math (see the row loop).
 //
@@ -487,7 +585,12 @@ __device__ __forceinline__ void dma16_nt(const void* g, unsigned lds) {
 // one loader wave that streams the block's rows through a ring of LOADER_SLOTS 16-KiB slots (see
 // the path's own comment).
 constexpr int LOADER = -1;
-constexpr int LOADER_SLOTS = 4;
+// 4 ships: with the loader outside the prologue a ring of 6 / 8 slots does run ahead through it,
+// but the row phase then takes 3–4 µs longer (39.2 / 40.5 vs 36.4 µs per round, profiles/r9).
+#ifndef FMLX_LOADER_SLOTS  // (A/B builds: -DFMLX_LOADER_SLOTS=4 | 6 | 8)
+#define FMLX_LOADER_SLOTS 4
+#endif
+constexpr int LOADER_SLOTS = FMLX_LOADER_SLOTS;
 constexpr int LOADER_SLOT_BYTES = 16384;  // 8 rows × 2 KiB
 template <typename T, int EPC, int CPL, int U, int WPB, bool NT, int DEPTH = 0>
 __global__ __launch_bounds__((WPB + (DEPTH < 0 ? 1 : 0)) * 64, (DEPTH < 0 ? 1 : glm_min_waves<T, EPC, CPL, U>())) void glm_round_kernel(
@@ -703,16 +806,33 @@ __global__ __launch_bounds__((WPB + (DEPTH < 0 ? 1 : 0)) * 64, (DEPTH < 0 ? 1 : 
     // DMA). Phase k: the loader issues step k + S − 2 into the slot read in phase k − 2 — those
     // ds_reads retired (lgkmcnt(0)) before the readers reached phase k − 1's barrier, which the
     // loader has passed — then waits with a counted vmcnt until step k has landed, then the
-    // barrier; the consumers read step k's slot only after that barrier. S − 2 fills are issued
-    // before the deferred prologue, so the ring fills while the prologue runs. vmcnt counts at
-    // most 63 loads: 16·(S − 1) = 48 outstanding at most with S = 4.
+    // barrier; the consumers read step k's slot only after that barrier. The lookahead stays S − 2,
+    // prefill included: with S − 1 the refilled slot would be one the consumers may still read.
+    // vmcnt counts at most 63 loads, so the counted wait is min(PIECES·(S − 2), 63): 32 with the
+    // shipped S = 4, 48 loads outstanding at most. From S = 6 on (A/B builds) the wait is vacuous
+    // and the hardware does the counting: a wave cannot issue a load while 63 of its loads are
+    // outstanding, and loads return in order, so when the last load of step k + S − 2 has gone
+    // out, the (at most) 63 outstanding ones are steps k + S − 2, k + S − 3, k + S − 4 and 15
+    // loads of step k + S − 5; step k <= k + S − 6 has landed.
+    // Prologue (deferred TAIL_UPDATE): the loader issues its S − 2 prefill steps and takes no part
+    // in the round completion (defer_prologue_consumers: the 8 consumer waves do it, in one memory
+    // round trip); it meets them at one raw s_barrier and reads the stop decision from LDS. Inside
+    // the prologue it stalled behind its own DMA: 5.2 µs from block start to prologue end,
+    // profiles/r9/lr_block_timeline_parent.jsonl. defer_prologue_xgmi has another barrier count
+    // per block role and keeps the loader inside: two steps go out before it, the rest of the
+    // prefill after it. The ticketed tail has no prologue.
+    // A deeper ring lets the loader run ahead through the prologue (S = 8: 4 of 6 prefetched
+    // steps landed at its end) but measured 3–4 µs per round slower in the row phase, also with
+    // the loads in flight capped at 48 (profiles/r9/INDEX.md), so S stays 4.
     // (scripts/stream_probe_loader.hip, profiles/r7/lr_probe_loader.log: this structure with the
     // round's math streams a 200 MB batch in 31.3–31.6 µs on 224 blocks; the register loop with no
     // math at all takes 32.2–32.6.)
     static_assert(sizeof(T) == 2 && EPC == 8 && CPL == 2 && U == 1, "loader path: bf16 rows of 65-128 chunks, U = 1");
     constexpr int S = LOADER_SLOTS;
     constexpr int PIECES = 2 * WPB;  // DMA loads per slot
-    static_assert(PIECES * (S - 1) <= 63, "vmcnt counts 63 loads");
+    constexpr int NWAIT = PIECES * (S - 2) < 63 ? PIECES * (S - 2) : 63;
+    static_assert(S >= 4 && PIECES == 16 && (PIECES * (S - 1) <= 63 || S >= 6),
+                  "counted wait, or >= 64 loads between a step and its phase (see above)");
     extern __shared__ __align__(16) unsigned char smem_r[];
     typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
     typedef __attribute__((address_space(3))) u32x4_t lds_u4_t;
@@ -744,30 +864,55 @@ __global__ __launch_bounds__((WPB + (DEPTH < 0 ? 1 : 0)) * 64, (DEPTH < 0 ? 1 : 
         }
       }
     };
+    // The two roles share no code from here to the end of the rows: a join between them makes the
+    // compiler wait for vmcnt(0) in the loader wave (the consumers' label loads are pending on one
+    // side of it), which drains the DMA.
+    const bool xg = tl.mode == TAIL_XGMI;
+    // the block's stop word follows its w image (launch_grad_k sizes it)
+    int* stopw = reinterpret_cast<int*>(wdef + d);
+    long long t_pro = 0, t_land[S - 2] = {};
     if (loader) {
+      const int pre = tl.defer && xg ? 2 : S - 2;
 #pragma unroll
       for (int k = 0; k < S - 2; ++k)
-        if (k < nj) fill(k);
-    } else if (nj > 0) {
-      load_labels(0);
-    }
-    if (tl.defer && (tl.mode == TAIL_XGMI ? defer_prologue_xgmi<A>(tl, coef, state, e, d, wdef)
-                                          : defer_prologue<A>(tl, coef, state, e, d, wdef))) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA may land after the wave exits
-      return;
-    }
-    if (nj > 0) {
-      if (loader) {
-        for (long k = 0; k < nj; ++k) {
-          if (k + S - 2 < nj) {
-            fill(k + S - 2);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PIECES * (S - 2)) : "memory");  // step k landed
-          } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          }
-          __builtin_amdgcn_s_barrier();
+        if (k < pre && k < nj) fill(k);
+      if (tl.defer) {
+        bool stop;
+        if (xg) {
+          stop = defer_prologue_xgmi<A>(tl, coef, state, e, d, wdef);
+        } else {
+          __builtin_amdgcn_s_barrier();  // the prologue's __syncthreads()
+          // (an LDS-typed read: a flat one would wait for vmcnt(0), i.e. for the DMA)
+          stop = __builtin_amdgcn_readfirstlane(*(const volatile __attribute__((address_space(3))) int*)stopw) != 0;
         }
-      } else {
+        if (stop) {
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA may land after the wave exits
+          return;
+        }
+#pragma unroll
+        for (int k = 2; k < S - 2; ++k)
+          if (xg && k < nj) fill(k);
+      }
+      if (tl.trace) {
+        t_pro = (long long)__builtin_amdgcn_s_memrealtime();
+        if (nj >= S - 2) stamp_landed<0, S - 2, PIECES>(t_land);
+      }
+      for (long k = 0; k < nj; ++k) {
+        if (k + S - 2 < nj) {
+          fill(k + S - 2);
+          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NWAIT) : "memory");  // step k landed
+        } else {
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        __builtin_amdgcn_s_barrier();
+      }
+    } else {
+      if (nj > 0) load_labels(0);
+      if (tl.defer && (xg ? defer_prologue_xgmi<A>(tl, coef, state, e, d, wdef)
+                          : defer_prologue_consumers<A, WPB * 64>(tl, coef, state, e, d, wdef, stopw)))
+        return;
+      if (tl.trace && wave == 0) t_pro = (long long)__builtin_amdgcn_s_memrealtime();
+      if (nj > 0) {
         load_w();
         for (long k = 0; k < nj; ++k) {
           __builtin_amdgcn_s_barrier();
@@ -793,6 +938,16 @@ __global__ __launch_bounds__((WPB + (DEPTH < 0 ? 1 : 0)) * 64, (DEPTH < 0 ? 1 : 
     // the epilogue's LDS buffers alias the ring: the loader has drained its DMA (vmcnt(0) in its
     // last phases) and every consumer is past its last read
     __syncthreads();
+    if (tl.trace && lane == 0 && (loader || wave == 0)) {
+      long long* tr = tl.trace + (long)blockIdx.x * TRACE_REC;
+      if (loader) {
+        tr[TRACE_LOADER] = t_pro;
+#pragma unroll
+        for (int i = 0; i < S - 2; ++i) tr[TRACE_LOADER + 1 + i] = t_land[i];
+      } else {
+        tr[TRACE_PROLOGUE] = t_pro;
+      }
+    }
   } else {
   const long step = (long)U * W;
   long r = start + gw;
@@ -850,7 +1005,7 @@ __global__ __launch_bounds__((WPB + (DEPTH < 0 ? 1 : 0)) * 64, (DEPTH < 0 ? 1 : 
     // has its own barrier)
     __syncthreads();
     if (threadIdx.x == 0) {
-      long long* tr = tl.trace + (long)blockIdx.x * 4;
+      long long* tr = tl.trace + (long)blockIdx.x * TRACE_REC;
       tr[0] = t_start;
       tr[1] = (long long)__builtin_amdgcn_s_memrealtime();
       unsigned hw;
@@ -909,7 +1064,7 @@ __global__ __launch_bounds__((WPB + (DEPTH < 0 ? 1 : 0)) * 64, (DEPTH < 0 ? 1 : 
     if (tl.trace) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if (threadIdx.x == 0) tl.trace[(long)blockIdx.x * 4 + 2] = (long long)__builtin_amdgcn_s_memrealtime();
+      if (threadIdx.x == 0) tl.trace[(long)blockIdx.x * TRACE_REC + 2] = (long long)__builtin_amdgcn_s_memrealtime();
     }
     if (tl.defer) return;  // launch e + 1 completes this round
     glm_round_tail_atomic<A>(tl, d, coef, state, e, buf, sflag);
@@ -1312,7 +1467,8 @@ template <typename T, int EPC, int CPL, int U, int PATH>
 int launch_grad_k(const RoundArgs& a, GlmTail t2, bool nt, hipStream_t s) {
   typedef typename AccOf<T>::type A;
   // epilogue LDS: [WPB or WPB/2][d] wave rows | [WPB][2] | ticket flag; the loader path's row ring
-  // starts at 0 and the epilogue buffers alias it; the deferred mode's w image follows both
+  // (LOADER_SLOTS × 16 KiB) starts at 0 and the epilogue buffers alias it;
+  // the deferred mode's w image follows both
   const size_t tail = (size_t)(t2.flat_lds ? WPB : WPB / 2) * a.d * sizeof(A) + WPB * 2 * sizeof(A) + 16;
   const size_t ring = PATH == LOADER ? (size_t)LOADER_SLOTS * LOADER_SLOT_BYTES : 0;
   constexpr int NW = WPB + (PATH == LOADER ? 1 : 0);  // the loader path adds its loader wave
@@ -1320,7 +1476,8 @@ int launch_grad_k(const RoundArgs& a, GlmTail t2, bool nt, hipStream_t s) {
   t2.ring_off = 0;
   if (t2.defer) {
     t2.wl_off = (int)((shmem + 15) & ~(size_t)15);
-    shmem = (size_t)t2.wl_off + (size_t)a.d * sizeof(A);
+    // (the loader path's stop word follows the image)
+    shmem = (size_t)t2.wl_off + (size_t)a.d * sizeof(A) + (PATH == LOADER ? 16 : 0);
     if (t2.mode == TAIL_XGMI) {  // the lead block's exchange row (never aliased with the ring)
       t2.xb_off = (int)((shmem + 15) & ~(size_t)15);
       shmem = (size_t)t2.xb_off + (size_t)(a.d + 2) * sizeof(A);
@@ -1486,7 +1643,7 @@ FMLX_API int fmlx_glm_set_tuning(long lds_pad, int nt) {
   return 0;
 }
 
-// diagnostics: launches record per-block timestamps into trace[nblocks][4] (null: off)
+// diagnostics: launches record per-block timestamps into trace[nblocks][TRACE_REC = 16] (null: off)
 FMLX_API void fmlx_glm_set_trace(void* trace) {
   g_trace = (long long*)trace;
   fmlx_glm_sparse_set_trace(trace);

@@ -68,19 +68,23 @@ def set_tail_tuning(acc_reps: int = 4, ticket2: bool = False) -> None:
 
 # Row path of the fused round for bf16 rows of d 513–1024 (csrc/glm.hip, DEPTH). FMLX_GLM_DMA:
 #  -1  automatic (default): streamed batches (non-temporal loads) on at most one block per CU take
-#      the loader/consumer path — a ninth wave per block fills a ring of four 16-KiB LDS slots (one
-#      step's 8 consecutive rows each) by global_load_lds behind a counted vmcnt, and hands each
-#      slot to the 8 consumer waves over one raw s_barrier per step; the consumers keep the register
-#      loop's row -> (block, wave, order) mapping and math, at 112 VGPRs instead of 148. Everything
+#      the loader/consumer path — a ninth wave per block fills a ring of LOADER_SLOTS 16-KiB LDS
+#      slots (one step's 8 consecutive rows each) by global_load_lds, up to 63 loads in flight, and
+#      hands each slot to the 8 consumer waves over one raw s_barrier per step; the consumers keep
+#      the register loop's row -> (block, wave, order) mapping and math, at 112 VGPRs instead of
+#      148. The loader runs LOADER_SLOTS − 2 steps ahead and stays out of the deferred round
+#      completion, so the ring fills while the consumers complete the previous round. Everything
 #      else takes register loads. Grid: round_blocks (224 for this layout).
 #      Streaming probe profiles/r7/lr_probe_loader.log; kernel and driver A/B against
-#      FMLX_GLM_DMA=0 profiles/r7/lr_loader_ab_1gpu.jsonl, lr_bench_loader_ab.log
+#      FMLX_GLM_DMA=0 profiles/r7/lr_loader_ab_1gpu.jsonl, lr_bench_loader_ab.log; the run-ahead
+#      ring against the four-slot one that waited through the prologue: profiles/r9/INDEX.md
 #   0  16-byte register loads, two steps of U rows per wave in flight (the round 3–6 kernel)
 # Any other value is refused at the first use. (Values 2–4 used to select a per-wave LDS-DMA ring of
 # that many steps, round 4. It measured slower — every wave issued its own DMA between its own
 # math, profiles/r4/lr_lds_dma_ring_ab_1gpu.jsonl —, the loader path superseded it, and it was
 # removed in round 8.)
 DMA_DEPTH = int(os.environ.get("FMLX_GLM_DMA", "-1"))
+LOADER_SLOTS = 4  # ring slots of the loader/consumer path (csrc/glm.hip LOADER_SLOTS)
 
 
 def set_dma(path: int) -> None:
@@ -98,7 +102,9 @@ def row_path() -> int:
 
 def set_trace(buf: Optional[torch.Tensor]) -> None:
     """Diagnostics: fused-round launches write per-block {start, rows done, atomics drained, hw
-    id} s_memrealtime stamps (100 MHz) into ``buf`` (int64 [blocks, 4]); None switches off."""
+    id, prologue done, loader past the prologue, prefetched step 0, 1, … landed} s_memrealtime
+    stamps (100 MHz) into ``buf`` (int64 [blocks, 16], csrc/glm.hip TRACE_REC; the sparse rounds
+    keep their own [blocks, 4] record); None switches off."""
     native.kernels().fmlx_glm_set_trace(native.ptr(buf))
 
 

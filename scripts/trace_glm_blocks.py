@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """Per-block timeline of the fused LR round at the bench shape (10M × 1000 bf16, 100k batch,
-256 blocks): start, rows-done and atomics-drained stamps (s_memrealtime, 100 MHz) of every block,
-summarised per round as spreads relative to the earliest block start, plus per-XCD means.
+the shape's default grid): start, prologue-done, rows-done and atomics-drained stamps
+(s_memrealtime, 100 MHz) of every block, summarised per round as spreads relative to the earliest
+block start, plus per-XCD means; then the three spans of a block (start → prologue done → rows
+done → end) as per-block medians and spreads. On the loader/consumer row path the loader wave also
+stamps when it got past the prologue and when it saw each prefetched ring step landed (it drains
+its prefetch for that, so a traced round starts its ring a little later than an untraced one):
+"steps landed" counts the prefetched steps that were in LDS when the prologue ended.
 
-Shows how much of a round is launch skew, load imbalance (the slowest block's rows) and tail.
+Shows how much of a round is launch skew, prologue, load imbalance (the slowest block's rows) and
+tail.
 Usage: python scripts/trace_glm_blocks.py [--rounds 20] [--defer 1]
 """
 import argparse
@@ -21,6 +27,11 @@ from flink_ml_amd.common.optimizer import SGD, DeviceGlmTrainer  # noqa: E402
 from flink_ml_amd.ops import glm as gk  # noqa: E402
 
 TICK_US = 0.01  # s_memrealtime runs at 100 MHz
+REC = 16  # int64 words per block (csrc/glm.hip TRACE_REC)
+PROLOGUE, LOADER = 4, 5  # (TRACE_PROLOGUE, TRACE_LOADER: loader past the prologue, then one per prefetched step)
+# a prefetched step counts as landed at the end of the prologue when the loader's wait for it
+# returned within this many ticks of the previous stamp (one s_memrealtime read takes 3–6)
+LANDED_TICKS = 10
 
 
 def main():
@@ -44,7 +55,7 @@ def main():
     tr.run_rounds(30)
     torch.cuda.synchronize()
     nb = tr.nparts
-    buf = torch.zeros((nb, 4), dtype=torch.int64, device=dev)
+    buf = torch.zeros((nb, REC), dtype=torch.int64, device=dev)
     gk.set_trace(buf)
     rows = []
     try:
@@ -84,11 +95,42 @@ def main():
                       "slowest_xcd_per_round": slow,
                       "block_done_spread_us_if_per_block_mean_removed": round(float(
                           np.median(np.ptp(done - done.mean(0, keepdims=True), axis=1)) * TICK_US), 2)}))
+    spans(rows)
     keys = ["start_max_us", "rows_done_min_us", "rows_done_med_us", "rows_done_max_us", "block_rows_us_med"]
     xm = {x: round(statistics.median(s["rows_done_mean_by_xcd"][x] for s in summary), 2)
           for x in summary[0]["rows_done_mean_by_xcd"]}
     print(json.dumps({"median_over_rounds": {k: round(statistics.median(s[k] for s in summary), 2) for k in keys},
                       "rows_done_mean_by_xcd_median": xm, "blocks": nb}))
+
+
+def spans(rows):
+    """Per-block spans over all rounds: median, 10th–90th percentile and maximum in µs, and the
+    loader wave's landed-step census (blocks whose record carries no prologue stamp, i.e. any row
+    path but the loader's, print only the whole-round spans)."""
+    t = np.stack(rows).astype(np.float64)  # [rounds, blocks, REC]
+
+    def stat(x):
+        x = x.reshape(-1) * TICK_US
+        return {"med": round(float(np.median(x)), 2), "p10": round(float(np.percentile(x, 10)), 2),
+                "p90": round(float(np.percentile(x, 90)), 2), "max": round(float(x.max()), 2)}
+
+    out = {"rows_done_to_end_us": stat(t[:, :, 2] - t[:, :, 1])}
+    if (t[:, :, PROLOGUE] > 0).all():
+        out["start_to_prologue_done_us"] = stat(t[:, :, PROLOGUE] - t[:, :, 0])
+        out["prologue_done_to_rows_done_us"] = stat(t[:, :, 1] - t[:, :, PROLOGUE])
+        ld = t[:, :, LOADER:]
+        ns = int((ld[0, 0] > 0).sum()) - 1  # prefetched steps
+        if ns > 0:
+            d = np.diff(ld[:, :, :ns + 1], axis=2)  # wait for step i, from the previous stamp
+            landed = (np.cumprod(d <= LANDED_TICKS, axis=2)).sum(axis=2)
+            out["prefetched_steps"] = ns
+            out["steps_landed_at_prologue_end"] = {"med": float(np.median(landed)), "min": int(landed.min()),
+                                                   "max": int(landed.max()), "mean": round(float(landed.mean()), 2)}
+            out["loader_wait_per_step_us_med"] = [round(float(np.median(d[:, :, i])) * TICK_US, 2) for i in range(ns)]
+            out["start_to_last_prefetched_step_landed_us"] = stat(ld[:, :, ns] - t[:, :, 0])
+    else:
+        out["start_to_rows_done_us"] = stat(t[:, :, 1] - t[:, :, 0])
+    print(json.dumps({"block_spans": out}))
 
 
 if __name__ == "__main__":
