@@ -143,12 +143,36 @@ def _dct_matrix(n: int) -> torch.Tensor:
     return dct_matrix(n)  # orthonormal DCT-II basis (rows)
 
 
+# Smallest n from which device rows wider than 128 take the FFT kernel (ops/csrc/dct_wide.hip)
+# instead of the GEMM with a resident basis, per (row type, n a power of two or not): measured,
+# profiles/r10/INDEX.md. Whatever these say, a size the kernel supports takes it once its basis
+# would reach DCT_WIDE_BASIS_CAP bytes, so no such n × n matrix is ever built or cached.
+# A power of two is one FFT of length n; any other n is two FFTs of length 2n … 4n per row (Bluestein),
+# which the GEMM beats at small n and again just above each power of two up to 2400 in f32.
+DCT_WIDE_FROM = {(torch.float32, True): 512, (torch.float32, False): 2600,
+                 (torch.float64, True): 256, (torch.float64, False): 1300}
+DCT_WIDE_BASIS_CAP = 64 << 20
+
+
+def _dct_takes_wide(n: int, dt: torch.dtype) -> bool:
+    from ...ops.dct import dct_wide_supported
+
+    if not dct_wide_supported(n, dt):
+        return False
+    itemsize = 8 if dt == torch.float64 else 4
+    return n >= DCT_WIDE_FROM[(dt, n & (n - 1) == 0)] or n * n * itemsize >= DCT_WIDE_BASIS_CAP
+
+
 @rw.register_stage
 class DCT(Transformer, HasInputCol, HasOutputCol):
-    """Orthonormal DCT-II / DCT-III (JTransforms ``DoubleDCT_1D`` with scaled=true, DCT.java:103-123)
-    as a product with the basis. K17 on the GPU: rows of n ≤ 128 go through the hand-written MFMA
-    kernels with the basis resident in LDS (``ops/csrc/dct.hip``: f32, and f64 in parity mode on
-    the f64 MFMA); wider rows and the CPU take the same product as a plain GEMM."""
+    """Orthonormal DCT-II / DCT-III (JTransforms ``DoubleDCT_1D`` with scaled=true, DCT.java:103-123).
+    K17 on the GPU: rows of n ≤ 128 are a product with the basis on the hand-written MFMA kernels,
+    the basis resident in LDS (``ops/csrc/dct.hip``: f32, and f64 in parity mode on the f64 MFMA).
+    Wider device rows, up to 16384 (f32) / 8192 (f64) for a power of two and 8191 / 4095 for any
+    other n, take the O(n log n) FFT kernel (``ops/csrc/dct_wide.hip``: Makhoul's permutation, one
+    DFT per row in LDS — Bluestein's for an n that is no power of two — tables of O(n), no n × n
+    basis) from the measured crossover ``DCT_WIDE_FROM`` on. Rows beyond those limits, sizes below
+    the crossover and the CPU take the product with the fp64 basis as a plain GEMM."""
 
     JAVA_CLASS_NAME = "org.apache.flink.ml.feature.dct.DCT"
     INVERSE = BooleanParam("inverse", "Whether to perform the inverse DCT (true) or forward DCT (false).", False)
@@ -164,6 +188,10 @@ class DCT(Transformer, HasInputCol, HasOutputCol):
             from ...ops.dct import dct_rows
 
             return [t.with_column(self.get(self.OUTPUT_COL), dct_rows(Xd, inv))]
+        if Xd.is_cuda and n > 128 and _dct_takes_wide(n, dt):
+            from ...ops import dct as dk
+
+            return [t.with_column(self.get(self.OUTPUT_COL), dk.dct_rows_wide(Xd, inv))]
         M = _dct_matrix(n).to(device=X.device, dtype=dt)
         out = Xd @ M if inv else Xd @ M.T
         return [t.with_column(self.get(self.OUTPUT_COL), out)]
