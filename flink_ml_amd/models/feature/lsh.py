@@ -6,16 +6,15 @@ MinHashLSHModel,MinHashLSHModelData}.java``).
 * transform: one ``minhash.hip`` launch over the CSR nonzero pattern → a [n, tables, funcs]
   fp64 tensor column (each row reads back as ``DenseVector[]``).
 * approx_nearest_neighbors: bucket filter (any table whose signature equals the key's), device
-  Jaccard distances from sorted-key membership, per-rank top-k then a global top-k; each rank
-  returns its own rows of the global answer.
-* approx_similarity_join: on one rank, a join on (table, signature) via ``unique(dim=0)`` group ids,
-  deduplicated candidate pairs, Jaccard distance <= threshold; across ranks the reference's keyed
-  join (``_keyed_similarity_join``: signature entries all-to-all'ed to their key owners, pairs to
-  their A row's rank, B sets fetched on demand) — a broadcast of B only for non-numeric ids.
+  Jaccard distances, per-rank top-k (``ops.lsh.nearest``: ``lsh_join.hip`` on a GPU) then a global
+  top-k; each rank returns its own rows of the global answer.
+* approx_similarity_join: on one rank, a join on (table, signature), deduplicated candidate pairs,
+  Jaccard distance <= threshold (``ops.lsh.similarity_join``: ``lsh_join.hip`` on a GPU); across
+  ranks the reference's keyed join (``_keyed_similarity_join``: signature entries all-to-all'ed to
+  their key owners, pairs to their A row's rank, B sets fetched on demand, distances from
+  ``ops.lsh.pair_jaccard``) — a broadcast of B only for non-numeric ids.
 """
 from __future__ import annotations
-
-from typing import List, Tuple
 
 import numpy as np
 import torch
@@ -63,36 +62,9 @@ def _sets(X) -> SparseColumn:
     return lsh_ops.to_csr_sets(X)
 
 
-def _row_keys(sets: SparseColumn) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(row id per nnz, sorted key row*d + col) for membership tests."""
-    dev = sets.values.device
-    rows = torch.repeat_interleave(torch.arange(len(sets), device=dev), (sets.indptr[1:] - sets.indptr[:-1]).to(dev))
-    return rows, rows * sets.size + sets.indices.to(dev).long()
-
-
 def _pair_jaccard(sa: SparseColumn, sb: SparseColumn, ia: torch.Tensor, ib: torch.Tensor) -> torch.Tensor:
-    """Jaccard distance of set pairs (sa[ia[p]], sb[ib[p]]), vectorised over all nnz of the A side."""
-    dev = ia.device
-    if ia.numel() == 0:
-        return torch.zeros(0, dtype=torch.float64, device=dev)
-    a_ptr, b_ptr = sa.indptr.to(dev), sb.indptr.to(dev)
-    la = (a_ptr[ia + 1] - a_ptr[ia])
-    lb = (b_ptr[ib + 1] - b_ptr[ib])
-    # expand every pair by its A-side nnz, look the column up in B's row-keyed sorted index
-    pid = torch.repeat_interleave(torch.arange(ia.numel(), device=dev), la)
-    off = torch.arange(pid.numel(), device=dev) - torch.repeat_interleave(torch.cumsum(la, 0) - la, la)
-    cols = sa.indices.to(dev).long()[a_ptr[ia][pid] + off]
-    d = max(sa.size, sb.size)
-    _, bkeys = _row_keys(SparseColumn(sb.indptr, sb.indices, sb.values, d))
-    bkeys_sorted, _ = torch.sort(bkeys)
-    q = ib[pid] * d + cols
-    pos = torch.clamp(torch.searchsorted(bkeys_sorted, q), max=max(bkeys_sorted.numel() - 1, 0))
-    hit = (bkeys_sorted[pos] == q) if bkeys_sorted.numel() else torch.zeros_like(q, dtype=torch.bool)
-    inter = torch.zeros(ia.numel(), dtype=torch.float64, device=dev).index_add_(0, pid, hit.to(torch.float64))
-    union = (la + lb).to(torch.float64) - inter
-    if bool((union <= 0).any()):
-        raise ValueError("The union of two input sets must have at least 1 elements")
-    return 1.0 - inter / union
+    """Jaccard distance of set pairs (sa[ia[p]], sb[ib[p]])."""
+    return lsh_ops.pair_jaccard(sa, sb, ia, ib)
 
 
 @rw.register_stage
@@ -148,11 +120,7 @@ class MinHashLSHModel(ModelWithData, LSHModelParams):
                             torch.as_tensor(np.asarray(ks.indices, dtype=np.int32), device=dev),
                             torch.ones(len(ks.indices), dtype=torch.float64, device=dev), ks.size())
         kh = self.hash_function(kset.to(dev))[0]
-        cand = (H == kh[None]).all(dim=2).any(dim=1)
-        idx = torch.nonzero(cand, as_tuple=True)[0]
-        dist = _pair_jaccard(kset, sets, torch.zeros_like(idx), idx)
-        order = torch.argsort(dist, stable=True)[:k]
-        loc_idx, loc_dist = idx[order], dist[order]
+        loc_idx, loc_dist = lsh_ops.nearest(H, kh, sets, kset, k)
         if get_world_distributed():
             from ...parallel.context import get_context
 
@@ -194,26 +162,8 @@ class MinHashLSHModel(ModelWithData, LSHModelParams):
             hb = torch.cat([p[0] for p in parts]).to(dev)
             sb = SparseColumn.concat([p[1] for p in parts]).to(dev)
             ids_b = [x for p in parts for x in p[2]]
-        na, nb = ha.shape[0], hb.shape[0]
-        pairs = []
-        for tb in range(ha.shape[1]):
-            allk = torch.cat([ha[:, tb], hb[:, tb]])
-            _, g = torch.unique(allk, dim=0, return_inverse=True)
-            ga, gb = g[:na], g[na:]
-            ob = torch.argsort(gb, stable=True)
-            gbs = gb[ob]
-            lo = torch.searchsorted(gbs, ga)
-            hi = torch.searchsorted(gbs, ga, right=True)
-            cnt = hi - lo
-            ia = torch.repeat_interleave(torch.arange(na, device=dev), cnt)
-            off = torch.arange(ia.numel(), device=dev) - torch.repeat_interleave(torch.cumsum(cnt, 0) - cnt, cnt)
-            ib = ob[lo[ia] + off]
-            pairs.append(ia * nb + ib)
-        keys = torch.unique(torch.cat(pairs)) if pairs else torch.zeros(0, dtype=torch.int64, device=dev)
-        ia, ib = torch.div(keys, nb, rounding_mode="floor"), keys % nb if nb else keys
-        dist = _pair_jaccard(sa, sb, ia, ib)
-        keep = dist <= threshold
-        ia, ib, dist = ia[keep].cpu().tolist(), ib[keep].cpu().tolist(), dist[keep].cpu()
+        ia, ib, dist = lsh_ops.similarity_join(ha, hb, sa, sb, threshold)
+        ia, ib, dist = ia.cpu().tolist(), ib.cpu().tolist(), dist.cpu()
         ids_a = dataset_a.get_list(id_col)
         return Table({"datasetA.id": [ids_a[i] for i in ia], "datasetB.id": [ids_b[j] for j in ib], dist_col: dist},
                      num_rows=len(ia))
