@@ -40,9 +40,26 @@ def reservoir_sample_indices(n: int, k: int, seed: int) -> np.ndarray:
     return out[:cnt]
 
 
-def sample_rows(X: torch.Tensor, k: int, seed: int) -> np.ndarray:
+def _rows_f64(X, idx: torch.Tensor) -> np.ndarray:
+    """Rows ``idx`` of a dense tensor or a ``SparseColumn`` as a host fp64 array (a sparse column
+    densifies only these rows)."""
+    if isinstance(X, SparseColumn):
+        pos = idx.to(X.indptr.device).long()
+        start, end = X.indptr[pos].cpu().long(), X.indptr[pos + 1].cpu().long()
+        out = np.zeros((len(idx), X.size))
+        for i, (s, e) in enumerate(zip(start.tolist(), end.tolist())):
+            j = X.indices[s:e].cpu().long().numpy()
+            ok = (j >= 0) & (j < X.size)  # (an index out of range is reported by the kernels)
+            out[i, j[ok]] = X.values[s:e].to(torch.float64).cpu().numpy()[ok]
+        return out
+    return X[idx.to(X.device)].to(torch.float64).cpu().numpy()
+
+
+def sample_rows(X, k: int, seed: int) -> np.ndarray:
     """``DataStreamUtils.sample``: reservoir per rank (only the k chosen rows leave the device),
-    gather in rank order, reservoir again over the union."""
+    gather in rank order, reservoir again over the union. ``X``: a dense [n, D] tensor or a
+    ``SparseColumn`` (the same draws; only the chosen rows are densified)."""
+    n_rows, width = (len(X), X.size) if isinstance(X, SparseColumn) else (int(X.shape[0]), int(X.shape[1]))
     draw_dev = X.device if X.device.type == "cuda" else config.compute_device()
     if draw_dev.type == "cuda":
         # the n-long draw stream in parallel on the device (bit-exact; ops/datagen.py); only the
@@ -50,13 +67,13 @@ def sample_rows(X: torch.Tensor, k: int, seed: int) -> np.ndarray:
         # the GPU, the k rows are gathered on the host)
         from ..ops.datagen import reservoir_sample_device
 
-        idx = reservoir_sample_device(int(X.shape[0]), k, seed, draw_dev)
+        idx = reservoir_sample_device(n_rows, k, seed, draw_dev)
     else:
-        idx = torch.as_tensor(reservoir_sample_indices(int(X.shape[0]), k, seed))
-    local = X[idx.to(X.device)].to(torch.float64).cpu().numpy() if len(idx) else np.zeros((0, X.shape[1]))
+        idx = torch.as_tensor(reservoir_sample_indices(n_rows, k, seed))
+    local = _rows_f64(X, idx) if len(idx) else np.zeros((0, width))
     gathered = comm.all_gather_object(local)
     allrows = np.concatenate([g for g in gathered if g.shape[0] > 0], axis=0) if any(
-        g.shape[0] for g in gathered) else np.zeros((0, X.shape[1]))
+        g.shape[0] for g in gathered) else np.zeros((0, width))
     return allrows[reservoir_sample_indices(allrows.shape[0], k, seed)]
 
 
@@ -113,8 +130,11 @@ class KMeansModel(ModelWithData, KMeansModelParams):
         C, _ = self._model_state()
         if C.shape[0] > self.get(self.K):
             raise ValueError("number of centroids %d exceeds k=%d" % (C.shape[0], self.get(self.K)))
-        X = config.features_for_compute(t, self.get(self.FEATURES_COL), allow_sparse=False)
         metric = self.get(self.DISTANCE_MEASURE)
+        Xs = kk.csr_features(t, self.get(self.FEATURES_COL), C.shape[0])
+        if Xs is not None:
+            return [t.with_column(self.get(self.PREDICTION_COL), predict_csr(Xs, C, metric))]
+        X = config.features_for_compute(t, self.get(self.FEATURES_COL), allow_sparse=False)
         if X.device.type == "cuda":
             cb = kk.CentroidBuffers(C.shape[0], C.shape[1], X.device,
                                     torch.float64 if X.dtype == torch.float64 else torch.float32)
@@ -132,10 +152,11 @@ class KMeans(Estimator, KMeansParams):
     def fit(self, *inputs: Table) -> KMeansModel:
         t = inputs[0]
         fcol = self.get(self.FEATURES_COL)
-        Xh = config.host_features_if_oversized(t, fcol)  # larger than FMLX_HBM_BUDGET: stays on the host
-        X = Xh if Xh is not None else config.features_for_compute(t, fcol, allow_sparse=False)
         k = self.get(self.K)
         metric = self.get(self.DISTANCE_MEASURE)
+        Xs = kk.csr_features(t, fcol, k)  # a SparseColumn on the CSR path: never densified
+        Xh = None if Xs is not None else config.host_features_if_oversized(t, fcol)  # stays on the host
+        X = Xs if Xs is not None else Xh if Xh is not None else config.features_for_compute(t, fcol, allow_sparse=False)
         init = sample_rows(X, k, self.get_seed())
         if Xh is not None:
             from ..common.outofcore import hbm_budget, streamed_kmeans
@@ -159,8 +180,28 @@ def _graph_ok(ck, log: bool) -> bool:
             and (not ctx.is_distributed or ctx.backend == "nccl"))
 
 
-def kmeans_lloyd(X: torch.Tensor, init: np.ndarray, max_iter: int, metric: str):
-    """``maxIter`` Lloyd rounds; returns (centroids [k,D] f64, weights [k] f64)."""
+def _lloyd_result(cb, rnd, sparse: bool):
+    out = np.ascontiguousarray(cb.cent.to(torch.float64).cpu().numpy()), cb.weights.cpu().numpy()
+    if sparse:
+        kk.check_csr_error(cb, rnd)  # with the fit's final host sync: an index outside [0, D) was skipped
+    return out
+
+
+def predict_csr(X: SparseColumn, C: torch.Tensor, metric: str) -> torch.Tensor:
+    """Closest centroid of every row of a device-resident ``SparseColumn`` (int64)."""
+    if C.shape[1] != X.size:
+        raise ValueError("vector size %d does not match the centroids' %d" % (X.size, C.shape[1]))
+    cb = kk.SparseCentroidBuffers(C.shape[0], C.shape[1], X.device,
+                                  torch.float64 if X.values.dtype == torch.float64 else torch.float32)
+    cb.set(C)
+    pred = kk.assign_csr(X, cb, metric).to(torch.int64)
+    kk.check_csr_error(cb)
+    return pred
+
+
+def kmeans_lloyd(X, init: np.ndarray, max_iter: int, metric: str):
+    """``maxIter`` Lloyd rounds on a dense [n, D] tensor or, on a GPU, a ``SparseColumn`` (the CSR
+    round); returns (centroids [k,D] f64, weights [k] f64)."""
     from ..parallel.checkpoint import AlgorithmCheckpoint, fault_point
 
     kc, D = init.shape
@@ -170,12 +211,13 @@ def kmeans_lloyd(X: torch.Tensor, init: np.ndarray, max_iter: int, metric: str):
         start, st = restored
         init, counts0 = st["centroids"].numpy(), st["weights"]
     if X.device.type == "cuda":
-        acc = torch.float64 if X.dtype == torch.float64 else torch.float32
-        cb = kk.CentroidBuffers(kc, D, X.device, acc)
+        sparse = isinstance(X, SparseColumn)
+        acc = torch.float64 if (X.values if sparse else X).dtype == torch.float64 else torch.float32
+        cb = (kk.SparseCentroidBuffers if sparse else kk.CentroidBuffers)(kc, D, X.device, acc)
         cb.set(torch.as_tensor(init))
         if restored is not None:
             cb.weights.copy_(counts0.to(cb.weights.dtype))
-        rnd = kk.KMeansRound(X, kc, metric)
+        rnd = (kk.SparseKMeansRound if sparse else kk.KMeansRound)(X, kc, metric)
         log = tracing.rounds_enabled()
         if _graph_ok(ck, log) and max_iter - start >= 3:
             # the round is host-sync free: run it once eagerly (warm-up), capture ONE round into a
@@ -196,7 +238,7 @@ def kmeans_lloyd(X: torch.Tensor, init: np.ndarray, max_iter: int, metric: str):
                 for e in range(start + 1, max_iter):
                     fault_point(e)
                     g.replay()
-            out = cb.cent.to(torch.float64).cpu().numpy(), cb.weights.cpu().numpy()
+            out = _lloyd_result(cb, rnd, sparse)
             comm.check_collectives()
             return out
         with tracing.range("kmeans.fit"):
@@ -220,7 +262,7 @@ def kmeans_lloyd(X: torch.Tensor, init: np.ndarray, max_iter: int, metric: str):
                                       collective_ms=round(evs[1].elapsed_time(evs[2]), 4),
                                       bytes=int(payload.numel() * payload.element_size()))
                 ck.maybe_save(e + 1, lambda: {"centroids": cb.cent.to(torch.float64), "weights": cb.weights})
-        out = cb.cent.to(torch.float64).cpu().numpy(), cb.weights.cpu().numpy()
+        out = _lloyd_result(cb, rnd, sparse)
         comm.check_collectives()  # after the host sync: no round used a partial xGMI exchange
         return out
     C = torch.as_tensor(init, dtype=torch.float64)

@@ -861,8 +861,13 @@ class OnlineKMeansModel(_OnlineModelMixin, ModelWithData, OnlineKMeansModelParam
         ver = self._current(block=True)
         C = (ver[0].device_values().to(torch.float64) if isinstance(ver[0], DeviceCentroids)
              else torch.as_tensor(np.stack([c.to_array() for c in ver[0]]), dtype=torch.float64))
-        X = config.features_for_compute(t, self.get(self.FEATURES_COL), allow_sparse=False)
         metric = self.get(self.DISTANCE_MEASURE)
+        Xs = kk.csr_features(t, self.get(self.FEATURES_COL), C.shape[0])
+        if Xs is not None:
+            from .kmeans import predict_csr
+
+            return t.with_column(self.get(self.PREDICTION_COL), predict_csr(Xs, C, metric))
+        X = config.features_for_compute(t, self.get(self.FEATURES_COL), allow_sparse=False)
         if X.device.type == "cuda":
             cb = kk.CentroidBuffers(C.shape[0], C.shape[1], X.device,
                                     torch.float64 if X.dtype == torch.float64 else torch.float32)

@@ -330,3 +330,278 @@ def group_by_key(keys: torch.Tensor, k: int, chunk: int = 0, stable: bool = Fals
                 native.ptr(offsets), native.ptr(chunk_off), native.ptr(order), native.stream_ptr(dev))
     m = int(offsets[k].item())
     return order[:m], offsets, chunk_off
+
+
+# ------------------------------------------------------------------------------------------------
+# CSR feature columns (csrc/kmeans_csr.hip): assign / Lloyd round without an n x D matrix
+# ------------------------------------------------------------------------------------------------
+# FMLX_KMEANS_CSR: "0" = a SparseColumn is densified (the path before the CSR kernels), "1" = the
+# CSR path whenever csr_supported, "auto" = the CSR path when the densified matrix would exceed the
+# HBM budget or the density nnz / (n·D) is at most CSR_CROSSOVER.
+CSR_ROUTE = os.environ.get("FMLX_KMEANS_CSR", "auto")
+# the highest density of the measured sweep (100,000 rows, k = 10 and 100; scripts/
+# bench_kmeans_sparse.py, profiles/r12/INDEX.md) at which the CSR round beat the densified one in
+# both run orders for both k: at 20 % the dense round wins at k = 10
+CSR_CROSSOVER = 0.05
+# columns of the column-major copy longer than this are summed in segments of this length, one
+# wave each, and their partial sums added in segment order (text columns are Zipf-distributed: one
+# wave per column would run as long as the most frequent term)
+CSR_COL_SEGMENT = 4096
+CSR_MAX_K = 1024
+
+
+def csr_kp(k: int) -> int:
+    """Lanes per row of the centroid image: k rounded up to a power of two (<= 64), above that to
+    64 · {1, 2, 4, 8, 16} (the accumulators a lane holds)."""
+    kp = 1
+    while kp < k:
+        kp *= 2
+    return kp
+
+
+def _elem(dtype) -> int:
+    return torch.empty(0, dtype=dtype).element_size()
+
+
+def csr_supported(X, k: int, device) -> bool:
+    """The CSR kernels take this column: a GPU, k <= 1024, 32-bit rows / entries, and the centroid
+    image, the payload and the column-major copy within the HBM budget."""
+    from ..table import SparseColumn
+
+    device = torch.device(device)
+    if device.type != "cuda" or not isinstance(X, SparseColumn):
+        return False
+    n, D, nnz = len(X), X.size, int(X.indices.numel())
+    if not (1 <= k <= CSR_MAX_K) or D < 1 or n >= 2 ** 31 or nnz >= 2 ** 31 or D >= 2 ** 31:
+        return False
+    from ..common.outofcore import hbm_budget
+
+    budget = hbm_budget(device)
+    es = 8 if X.values.dtype == torch.float64 else 4
+    need = 2 * D * csr_kp(k) * es + nnz * (4 + es) * 2 + 16 * nnz + 8 * (n + D)
+    return budget is None or need <= budget
+
+
+def csr_route(X, k: int, device) -> bool:
+    """Whether a SparseColumn takes the CSR path (``CSR_ROUTE``)."""
+    if CSR_ROUTE == "0" or not csr_supported(X, k, device):
+        return False
+    if CSR_ROUTE == "1":
+        return True
+    from .. import config
+    from ..common.outofcore import hbm_budget
+
+    n, D, nnz = len(X), X.size, int(X.indices.numel())
+    budget = hbm_budget(device)
+    if budget is not None and n * D * _elem(config.compute_dtype()) > budget:
+        return True
+    return nnz <= CSR_CROSSOVER * n * D
+
+
+def csr_features(table, col: str, k: int):
+    """The feature column as a device-resident ``SparseColumn`` (values in the accumulation dtype)
+    when it is one and takes the CSR path, else None (the caller densifies as before)."""
+    from .. import config
+    from ..table import SparseColumn
+
+    c = table.column(col)
+    dev = config.compute_device()
+    if not isinstance(c, SparseColumn) or not csr_route(c, k, dev):
+        return None
+    return config.features_for_compute(table, col, allow_sparse=True)
+
+
+def _csr_arrays(X, dtype):
+    return (X.indptr.to(torch.int64).contiguous(), X.indices.to(torch.int32).contiguous(),
+            X.values.to(dtype).contiguous())
+
+
+class SparseCentroidBuffers:
+    """The centroid image of the CSR kernels: centroid-minor ``Ct[D][kp]`` (padding lanes 0), the
+    per-centroid norms ``[‖c‖ | ‖c‖² | ‖c‖₁]`` and the weights. ``cent`` is its [k, D] view."""
+
+    def __init__(self, k: int, D: int, device, acc_dtype):
+        self.k, self.D = int(k), int(D)
+        self.kp = csr_kp(self.k)
+        self.Ct = torch.zeros((self.D, self.kp), dtype=acc_dtype, device=device)
+        self.norms = torch.zeros((3, self.kp), dtype=acc_dtype, device=device)
+        self.weights = torch.zeros(self.k, dtype=torch.float64, device=device)
+        # finalize: block b folds rows [b·rpb, (b + 1)·rpb) of the image, then one ordered add
+        self.rpb = max(256, -(-self.D // 1024))
+        self.nb = -(-self.D // self.rpb)
+        self.part = torch.zeros((self.nb, 2, self.kp), dtype=acc_dtype, device=device)
+        self.err = torch.zeros(1, dtype=torch.int32, device=device)
+
+    @property
+    def cent(self) -> torch.Tensor:
+        return self.Ct[:, : self.k].t()
+
+    def set(self, centroids: torch.Tensor) -> None:
+        # formed on the host and copied over once, like CentroidBuffers.set
+        c = torch.as_tensor(centroids).detach().to(device="cpu", dtype=torch.float64)
+        Ct = torch.zeros((self.D, self.kp), dtype=self.Ct.dtype)
+        Ct[:, : self.k] = c.t().to(self.Ct.dtype)
+        c = Ct[:, : self.k].t().to(torch.float64)
+        norms = torch.zeros((3, self.kp), dtype=torch.float64)
+        norms[1, : self.k] = (c * c).sum(1)
+        norms[0, : self.k] = norms[1, : self.k].sqrt()
+        norms[2, : self.k] = c.abs().sum(1)
+        self.Ct.copy_(Ct)
+        self.norms.copy_(norms.to(self.norms.dtype))
+
+
+def check_csr_error(*holders) -> None:
+    """Raises for a feature index outside [0, D) seen by a CSR kernel (the entry was skipped)."""
+    bad = 0
+    for h in holders:
+        bad |= int(h.err.item())
+    if bad:
+        raise ValueError("sparse feature index out of range [0, size)")
+
+
+def assign_csr(X, cb: SparseCentroidBuffers, metric: str, out: torch.Tensor = None) -> torch.Tensor:
+    """``assign`` for a device-resident ``SparseColumn``; a bad index sets ``cb.err``."""
+    n = len(X)
+    dev = cb.Ct.device
+    if X.size != cb.D:
+        raise ValueError("vector size %d does not match the centroids' %d" % (X.size, cb.D))
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return out
+    indptr, idx, val = _csr_arrays(X, cb.Ct.dtype)
+    native.call("fmlx_kmeans_csr_assign", int(cb.Ct.dtype == torch.float64), native.ptr(indptr), native.ptr(idx),
+                native.ptr(val), n, cb.D, native.ptr(cb.Ct), cb.kp, cb.k, native.ptr(cb.norms), METRICS[metric],
+                native.ptr(out), native.ptr(cb.err), native.stream_ptr(dev))
+    return out
+
+
+class SparseKMeansRound:
+    """One Lloyd iteration on a device-resident CSR partition: assign → per-column sums through the
+    column-major copy (built here, once per fit) → ``payload`` = ``[D·kp sums | k counts]``."""
+
+    def __init__(self, X, k: int, metric: str):
+        from . import glm as _glm
+
+        dev = X.values.device
+        self.n, self.D, self.k, self.metric = len(X), X.size, int(k), metric
+        self.kp = csr_kp(self.k)
+        self.acc = torch.float64 if X.values.dtype == torch.float64 else torch.float32
+        self.indptr, self.idx, self.val = _csr_arrays(X, self.acc)
+        self.X = type(X)(self.indptr, self.idx, self.val, self.D)
+        self.nnz = nnz = int(self.idx.numel())
+        self.seg = int(CSR_COL_SEGMENT)
+        self.labels = torch.empty(self.n, dtype=torch.int32, device=dev)
+        self.payload = torch.zeros(self.D * self.kp + self.k, dtype=self.acc, device=dev)
+        self.counts = torch.zeros(self.k, dtype=torch.int32, device=dev)  # re-zeroed by every round
+        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.colptr = torch.zeros(self.D + 1, dtype=torch.int64, device=dev)
+        self.crow = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
+        self.cval = torch.empty(max(nnz, 1), dtype=self.acc, device=dev)
+        stream = native.stream_ptr(dev)
+        if nnz:
+            # (column, entry id) through the stable segmented radix sort: one segment, ceil(log2 D)
+            # key bits; a column's entries stay in row order
+            bits = max(1, int(self.D - 1).bit_length())
+            keys = torch.empty(nnz, dtype=torch.int32, device=dev)
+            ids = torch.empty(nnz, dtype=torch.int32, device=dev)
+            erow = torch.empty(nnz, dtype=torch.int32, device=dev)
+            native.call("fmlx_kmeans_csr_prepare", native.ptr(self.indptr), native.ptr(self.idx), self.n, self.D,
+                        native.ptr(keys), native.ptr(ids), native.ptr(erow), native.ptr(self.err), stream)
+            keys, ids = _glm.seg_sort(keys, ids, [0, nnz], [0], bits)
+            native.call("fmlx_kmeans_csr_colptr", native.ptr(keys), nnz, self.D, native.ptr(self.colptr), stream)
+            native.call("fmlx_kmeans_csr_gather", int(self.acc == torch.float64), native.ptr(ids), native.ptr(erow),
+                        native.ptr(self.val), nnz, native.ptr(self.crow), native.ptr(self.cval), stream)
+            del keys, ids, erow  # the sort scratch goes with them
+        # columns longer than a segment: (column, first segment) and the per-segment table
+        lens = self.colptr[1:] - self.colptr[:-1]
+        long_col = torch.nonzero(lens > self.seg).reshape(-1)
+        self.nlong = int(long_col.numel())
+        nseg = (lens[long_col] + self.seg - 1) // self.seg
+        self.long_seg0 = torch.zeros(self.nlong + 1, dtype=torch.int64, device=dev)
+        self.long_seg0[1:] = torch.cumsum(nseg, 0)
+        self.nsegs = int(self.long_seg0[-1].item())
+        self.long_col = long_col.to(torch.int32)
+        self.seg_col = torch.repeat_interleave(self.long_col, nseg, output_size=self.nsegs)
+        self.seg_k = (torch.arange(self.nsegs, device=dev)
+                      - torch.repeat_interleave(self.long_seg0[:-1], nseg, output_size=self.nsegs)).to(torch.int32)
+        self.partial = torch.zeros(max(self.nsegs, 1) * self.kp, dtype=self.acc, device=dev)
+
+    def run(self, cb: SparseCentroidBuffers) -> torch.Tensor:
+        assign_csr(self.X, cb, self.metric, self.labels)
+        return self.colsum()
+
+    def colsum(self) -> torch.Tensor:
+        """The centroid update of the current ``labels`` into ``payload``."""
+        native.call("fmlx_kmeans_csr_colsum", int(self.acc == torch.float64), native.ptr(self.colptr),
+                    native.ptr(self.crow), native.ptr(self.cval), native.ptr(self.labels), self.n, self.D, self.kp,
+                    self.k, self.seg, self.nlong, native.ptr(self.long_col), native.ptr(self.long_seg0), self.nsegs,
+                    native.ptr(self.seg_col), native.ptr(self.seg_k), native.ptr(self.partial),
+                    native.ptr(self.counts), native.ptr(self.payload), native.stream_ptr(self.payload.device))
+        return self.payload
+
+    def finalize(self, cb: SparseCentroidBuffers, payload: torch.Tensor) -> None:
+        native.call("fmlx_kmeans_csr_finalize", int(self.acc == torch.float64), native.ptr(payload), self.D, self.kp,
+                    self.k, native.ptr(cb.Ct), native.ptr(cb.norms), native.ptr(cb.weights), native.ptr(cb.part),
+                    cb.rpb, cb.nb, native.stream_ptr(payload.device))
+
+
+def _csr_rows(X) -> torch.Tensor:
+    indptr = X.indptr.to(torch.int64)
+    n = len(X)
+    return torch.repeat_interleave(torch.arange(n, device=indptr.device), indptr[1:] - indptr[:-1],
+                                   output_size=int(X.indices.numel()))
+
+
+def torch_dist_csr(X, C: torch.Tensor, metric: str) -> torch.Tensor:
+    """Host reference: the [n, k] fp64 distances of ``torch_assign`` (squared for euclidean) for a
+    ``SparseColumn``, through torch's sparse-CSR ``@``: no n x D array is formed."""
+    import warnings
+
+    n, D = len(X), X.size
+    dev = X.values.device
+    indptr, idx, val = X.indptr.to(torch.int64), X.indices.to(torch.int64), X.values.to(torch.float64)
+    C = C.to(device=dev, dtype=torch.float64)
+    rows = _csr_rows(X)
+    cn = torch.linalg.vector_norm(C, dim=1)
+    pn = torch.zeros(n, dtype=torch.float64, device=dev).index_add_(0, rows, val * val).sqrt()
+    if metric == "manhattan":
+        d = C.abs().sum(1)[None, :].repeat(n, 1)
+        Ct = C.t().contiguous()
+        for s in range(0, int(idx.numel()), 1 << 16):
+            cj = Ct[idx[s:s + (1 << 16)]]
+            d.index_add_(0, rows[s:s + (1 << 16)], (val[s:s + (1 << 16), None] - cj).abs() - cj.abs())
+        return d
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        dot = torch.sparse_csr_tensor(indptr, idx, val, size=(n, D)) @ C.t().contiguous()
+    if metric == "euclidean":
+        return torch.clamp(pn[:, None] * pn[:, None] + (cn * cn)[None, :] - 2.0 * dot, min=0.0)
+    return 1.0 - dot / pn[:, None] / cn[None, :]
+
+
+def torch_assign_csr(X, C: torch.Tensor, metric: str) -> torch.Tensor:
+    """``torch_assign`` for a ``SparseColumn`` (fp64, no n x D array)."""
+    if len(X) == 0:
+        return torch.zeros(0, dtype=torch.int64)
+    d = torch_dist_csr(X, C, metric)
+    if metric == "euclidean":
+        d = torch.where(torch.isnan(d), torch.full_like(d, float("inf")), d)
+    return torch.argmin(d, dim=1)
+
+
+def torch_round_payload_csr(X, C: torch.Tensor, metric: str, labels: torch.Tensor = None) -> torch.Tensor:
+    """``torch_round_payload`` for a ``SparseColumn``: ``[k·D sums | k counts]`` in fp64 (of the given
+    ``labels`` instead of the reference assignment when passed; labels outside [0, k) add nothing)."""
+    k, D = C.shape
+    dev = X.values.device
+    out = torch.zeros(k * D + k, dtype=torch.float64, device=dev)
+    if len(X) == 0:
+        return out
+    lab = (torch_assign_csr(X, C, metric) if labels is None else labels.to(dev)).to(torch.int64)
+    ok = (lab >= 0) & (lab < k)
+    el = lab[_csr_rows(X)]
+    eok = (el >= 0) & (el < k)
+    out.index_add_(0, el[eok] * D + X.indices.to(torch.int64)[eok], X.values.to(torch.float64)[eok])
+    out[k * D:] = torch.bincount(lab[ok], minlength=k).to(torch.float64)
+    return out
