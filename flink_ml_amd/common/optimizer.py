@@ -227,17 +227,9 @@ class DeviceGlmTrainer:
             if c0.shape[0] < self.d:
                 c0 = np.concatenate([c0, np.zeros(self.d - c0.shape[0])])
         zero_init = c0 is None or not c0.size or int(c0.view(np.uint64).max()) == 0
-        self._zb = None
-        if (self.sparse and zero_init and dev.type == "cuda" and self.n > 0
-                and (bucket_nnz is not None or self._bucket_pays(sgd))):
-            # the bucket round's zero-initialised buffers — coefficients, round state, feedback,
-            # Σw/Σloss slots, the rounds' slice counters and accumulator — as ONE allocation and ONE
-            # fill launch (a short fit's GPU idles through every Python-side launch)
-            from ..ops import native
-
-            self._zb = native.zeros_many([((self.d,), acc), ((8,), torch.int32), ((self.d + 2,), acc),
-                                          ((gk.wl_elems(),), acc), ((gk.BucketRound.nb_for(self.d) + 16,), torch.int32),
-                                          ((self.d,), acc)], dev)
+        self.bkt = self.csc = None
+        self._zb = self._alloc_sparse_round(sgd, zero_init, bucket_nnz) if self.sparse else None
+        if self._zb is not None:
             self.coef, self.state, self.feedback = self._zb[:3]
         else:
             if zero_init:
@@ -256,7 +248,6 @@ class DeviceGlmTrainer:
             self.state[1:2].fill_(1)
         self.distributed = ctx.is_distributed
         self.xg = None
-        self.csc = None
         # dense rows one wave's registers cannot hold: the wide-row kernel (a block's 8 waves split
         # each row's columns, one read of the batch, fused atomic tail); beyond its width (or in
         # the deterministic mode) two bandwidth-bound GEMVs per round (X_b·w, then X_bᵀ·m,
@@ -267,36 +258,9 @@ class DeviceGlmTrainer:
         self.wide_fused = self.wide_layout is not None
         self.wide = not self.sparse and self.layout is None and not self.wide_fused
         self._host_round = 0
-        self.bkt = None
         if self.sparse:
             self.scratch = None
             self.nparts = 0
-            zb = self._zb
-            if bucket_nnz is not None:
-                # (the out-of-core trainer: one batch at a time, every round on the bucket path;
-                # bucket_nnz = (largest batch's entries, mean row length))
-                self.bkt = gk.BucketRound.alloc(self.indptr, self.values, max(1, self.n), self.d, self.B,
-                                                most=bucket_nnz[0], avg=bucket_nnz[1],
-                                                zero_bufs=None if zb is None else (zb[4], zb[5]))
-                if self.bkt is None:
-                    raise ValueError("streamed sparse batches need the bucket round (too many column slices)")
-                self.wl = zb[3] if zb is not None else _dzeros(gk.wl_elems(), acc, dev)
-            elif dev.type == "cuda" and self.n > 0 and self._bucket_pays(sgd):
-                # each batch visited a few times (the reference's regime): the single-visit round,
-                # nothing built per batch but the column-slice counts of the visited batches
-                P = -(-self.n // max(self.B, 1))
-                self.bkt = gk.BucketRound.alloc(self.indptr, self.values, self.n, self.d, self.B,
-                                                batches=min(P, sgd.max_iter),
-                                                zero_bufs=None if zb is None else (zb[4], zb[5]))
-                if self.bkt is not None:
-                    self.wl = zb[3] if zb is not None else _dzeros(gk.wl_elems(), acc, dev)
-            if self.bkt is None and dev.type == "cuda" and self.n > 0:
-                # allocated here, batches transposed lazily before the rounds that visit them
-                self.csc = gk.BatchCsc.alloc(self.indptr, self.indices, self.values, self.n, self.d, self.B,
-                                             max_rounds=sgd.max_iter)
-                if self.csc is not None:
-                    self.mult = _dzeros(max(1, min(self.B, self.n)), acc, dev)
-                    self.wl = _dzeros(gk.wl_elems(), acc, dev)  # Σw/Σloss slots per parity
         elif self.wide:
             self.scratch = None
             self.nparts = 0
@@ -375,6 +339,55 @@ class DeviceGlmTrainer:
             self.use_graph = False  # a gloo all-reduce of device tensors cannot be captured
         self.graphs.clear()
 
+    def _alloc_sparse_round(self, sgd: SGD, zero_init: bool, bucket_nnz):
+        """Chooses the sparse round form once and allocates for it: the single-visit bucket round
+        (``self.bkt``, ``self.wl``), the transposed round (``self.csc``, ``self.mult``, ``self.wl``)
+        or neither (the scattered-atomic kernel). Returns the bucket round's block of zeroed
+        buffers when it made one — coefficients, round state, feedback, Σw/Σloss slots, the rounds'
+        slice counters and accumulator as ONE allocation and ONE fill launch (a short fit's GPU
+        idles through every Python-side launch) — else None."""
+        dev, acc = self.device, self.acc
+        live = dev.type == "cuda" and self.n > 0
+        zb = None
+        if bucket_nnz is not None or (live and self._bucket_pays(sgd)):
+            if zero_init and live:
+                from ..ops import native
+
+                zb = native.zeros_many([((self.d,), acc), ((8,), torch.int32), ((self.d + 2,), acc),
+                                        ((gk.wl_elems(),), acc), ((gk.BucketRound.nb_for(self.d) + 16,), torch.int32),
+                                        ((self.d,), acc)], dev)
+            if bucket_nnz is not None:
+                # (the out-of-core trainer: one batch at a time, every round on the bucket path;
+                # bucket_nnz = (largest batch's entries, mean row length))
+                size = dict(most=bucket_nnz[0], avg=bucket_nnz[1])
+            else:
+                # each batch visited a few times (the reference's regime): the single-visit round,
+                # nothing built per batch but the column-slice counts of the visited batches
+                size = dict(batches=min(-(-self.n // max(self.B, 1)), sgd.max_iter))
+            self.bkt = gk.BucketRound.alloc(self.indptr, self.values, max(1, self.n), self.d, self.B,
+                                            zero_bufs=None if zb is None else (zb[4], zb[5]), **size)
+            if self.bkt is not None:
+                self.wl = zb[3] if zb is not None else _dzeros(gk.wl_elems(), acc, dev)
+            elif bucket_nnz is not None:
+                raise ValueError("streamed sparse batches need the bucket round (too many column slices)")
+        if self.bkt is None and live:
+            # allocated here, batches transposed lazily before the rounds that visit them
+            self.csc = gk.BatchCsc.alloc(self.indptr, self.indices, self.values, self.n, self.d, self.B,
+                                         max_rounds=sgd.max_iter)
+            if self.csc is not None:
+                self.mult = _dzeros(max(1, min(self.B, self.n)), acc, dev)
+                self.wl = _dzeros(gk.wl_elems(), acc, dev)  # Σw/Σloss slots per parity
+        return zb
+
+    def _reduce_and_update(self) -> None:
+        """The feedback tail of a round: all-reduce of the feedback row across the ranks, then the
+        device update kernel (SGD step, regularisation, termination check)."""
+        s = self.sgd
+        if self.distributed:
+            comm.all_reduce_sum(self.feedback)
+        gk.update(self.feedback, self.d, self.coef, self.state, s.max_iter, s.tol, s.learning_rate, s.reg,
+                  s.elastic_net)
+
     def _bucket_pays(self, sgd: SGD) -> bool:
         """The single-visit bucket round (no per-batch transpose) for fits that visit each batch
         fewer than ``gk.TILE_MIN_VISITS`` times; more visits amortise the transposed layout's
@@ -405,9 +418,7 @@ class DeviceGlmTrainer:
                          self.B, self.loss, self.state, self.wl, self.feedback, not self.distributed, s.max_iter, s.tol,
                          s.learning_rate, s.reg, s.elastic_net)
             if self.distributed:
-                comm.all_reduce_sum(self.feedback)
-                gk.update(self.feedback, self.d, self.coef, self.state, s.max_iter, s.tol, s.learning_rate, s.reg,
-                          s.elastic_net)
+                self._reduce_and_update()
             return
         if self.csc is not None:
             if ensure and not torch.cuda.is_current_stream_capturing():
@@ -418,17 +429,13 @@ class DeviceGlmTrainer:
                          self.B, self.loss, self.state, self.mult, self.wl, self.feedback, not self.distributed,
                          s.max_iter, s.tol, s.learning_rate, s.reg, s.elastic_net)
             if self.distributed:
-                comm.all_reduce_sum(self.feedback)
-                gk.update(self.feedback, self.d, self.coef, self.state, s.max_iter, s.tol, s.learning_rate, s.reg,
-                          s.elastic_net)
+                self._reduce_and_update()
             return
         if self.wide_fused:
             gk.glm_round_wide(self.X, self.y, self.w, self.coef, self.B, self.loss, self.state, self.scratch, self.mode,
                               self.feedback, s.max_iter, s.tol, s.learning_rate, s.reg, s.elastic_net)
             if self.mode == gk.TAIL_FEEDBACK:
-                comm.all_reduce_sum(self.feedback)
-                gk.update(self.feedback, self.d, self.coef, self.state, s.max_iter, s.tol, s.learning_rate, s.reg,
-                          s.elastic_net)
+                self._reduce_and_update()
             return
         if self.wide:
             # the device state advances once per launch whether or not the round runs, so the
@@ -449,20 +456,14 @@ class DeviceGlmTrainer:
                 self.feedback[self.d + 1] = l.sum()
             else:
                 self.feedback.zero_()
-            if self.distributed:
-                comm.all_reduce_sum(self.feedback)
-            gk.update(self.feedback, self.d, self.coef, self.state, s.max_iter, s.tol, s.learning_rate, s.reg,
-                      s.elastic_net)
+            self._reduce_and_update()
             return
         if self.sparse:
             self.feedback.zero_()
             if self.n > 0:
                 gk.grad_csr(self.indptr, self.indices, self.values, self.y, self.w, self.coef, self.n, self.d, self.B,
                             self.loss, self.state, self.feedback)
-            if self.distributed:
-                comm.all_reduce_sum(self.feedback)
-            gk.update(self.feedback, self.d, self.coef, self.state, s.max_iter, s.tol, s.learning_rate, s.reg,
-                      s.elastic_net)
+            self._reduce_and_update()
             return
         # every rank launches the round, also one without rows: it still joins the reduction tail
         gk.glm_round(self.X, self.y, self.w, self.coef, self.B, self.loss, self.state, self.scratch, self.mode,
@@ -471,9 +472,7 @@ class DeviceGlmTrainer:
         if self.defer:
             self.parity = (self.parity + rounds) & 1
         if self.mode == gk.TAIL_FEEDBACK:
-            comm.all_reduce_sum(self.feedback)
-            gk.update(self.feedback, self.d, self.coef, self.state, s.max_iter, s.tol, s.learning_rate, s.reg,
-                      s.elastic_net)
+            self._reduce_and_update()
 
     def _ensure_csc(self, first: int, k: int) -> None:
         """Column-major copies of the batches rounds first … first + k − 1 visit; rounds at or

@@ -1619,11 +1619,6 @@ GlmTail make_tail(int mode, int det, int* cnt, void* acc, void* stage1, void* fe
   return tl;
 }
 
-// the split path's accumulator type: f is called with a value of it
-template <typename F>
-int with_acc(int acc_f64, F&& f) {
-  return acc_f64 ? f(double{}) : f(float{});
-}
 #endif  // FMLX_ISA_PROBE
 }  // namespace
 

@@ -4,17 +4,32 @@
 // LIB/common/lossfunc/HingeLoss.java:39-57 (dot, hinge loss, axpy of the multiplier into the
 // gradient), the update of SGD.java:231-243 and RegularizationUtils.java:47-91.
 //
-// Three round forms, picked per fit by ops/glm.py (DeviceGlmTrainer):
+// Three round forms, picked per fit by common/optimizer.py (DeviceGlmTrainer):
 //  * single-visit bucket round (glm_bkt_*): the reference's regime (each batch visited once or a
 //    few times): nothing is precomputed per batch;
 //  * transposed rounds (glm_csr_fwd / glm_csr_cell_fwd + glm_csc_bwd / glm_csc_tile_bwd): batches
 //    visited many times (or FMLX_DETERMINISTIC=1) amortise a per-batch column-major copy
 //    (csc_build.hip) and run atomic-free, deterministic backward passes;
 //  * glm_grad_csr_kernel: the scattered-atomic fallback when neither fits.
+#include <type_traits>
+
 #include "common.h"
 #include "glm_core.h"
 
 namespace {
+
+// Round e visits batch e mod ⌈n / B⌉ (SGD.java:263-268); batch b is the fixed row range
+// [b·B, min((b + 1)·B, n)) (SGD.java:192-206 slicing). Two functions: the backward kernels need the
+// rows only on their unweighted branch (the end computed ahead of it, or written start + B, costs
+// the feedback backwards 8 SGPRs: profiles/r13).
+__device__ __forceinline__ long round_batch(int e, long n, long B) {
+  const long P = (n + B - 1) / B;
+  return (long)(e % P);
+}
+__device__ __forceinline__ void batch_rows(long b, long n, long B, long& start, long& end) {
+  start = b * B;
+  end = (b + 1) * B < n ? (b + 1) * B : n;
+}
 
 // ------------------------------------------------------------------------------------------
 // CSR (sparse features) gradient — a wave per row, gather dot, atomic scatter of mult·x into
@@ -28,9 +43,8 @@ __global__ __launch_bounds__(256) void glm_grad_csr_kernel(const long* __restric
                                                            A* __restrict__ grad /* d+2, zeroed */) {
   int e;
   if (!round_running(state, e)) return;
-  const long P = (n + B - 1) / B;
-  const long start = (long)(e % P) * B;
-  const long end = start + B < n ? start + B : n;
+  long start, end;
+  batch_rows(round_batch(e, n, B), n, B, start, end);
   const int lane = threadIdx.x & 63;
   const long gw = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const long W = ((long)gridDim.x * blockDim.x) >> 6;
@@ -99,6 +113,35 @@ __device__ __forceinline__ A group_sum(A v) {
 constexpr int WL_SLOTS = 256;  // Σweight/Σloss accumulator: [2 parities][WL_SLOTS][WL_STRIDE]
 constexpr int WL_STRIDE = 32;  // 128 B apart
 
+// A forward block's Σweight / Σloss into a parity slot of `wl`, in two steps (the bucket forward
+// stamps its trace between them). Stage: every wave's sums into `red`, then a barrier; the caller
+// passes wave_sum(...) of its threads' sums (made inside the helper, the fp32 forwards scheduled
+// their last adds differently: profiles/r13). Add: thread 0 adds the nw waves' sums to slot
+// `slot` mod WL_SLOTS of round e's parity — one of WL_SLOTS cache lines per block: same-address
+// float atomics from thousands of blocks serialise at the coherence point (measured: the
+// single-address version cost more than the row math); the backward sums the slots in a fixed order.
+template <int NW, typename A>
+__device__ __forceinline__ void fwd_sums_stage(A wave_w, A wave_l, A (&red)[2][NW]) {
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = wave_w;
+    red[1][threadIdx.x >> 6] = wave_l;
+  }
+  __syncthreads();
+}
+template <int NW, typename A>
+__device__ __forceinline__ void fwd_sums_add(const A (&red)[2][NW], int nw, A* __restrict__ wl, int e, int slot) {
+  if (threadIdx.x == 0) {
+    A a0 = 0, a1 = 0;
+    for (int i = 0; i < nw; ++i) {
+      a0 += red[0][i];
+      a1 += red[1][i];
+    }
+    A* s = wl + ((long)(e & 1) * WL_SLOTS + (slot & (WL_SLOTS - 1))) * WL_STRIDE;
+    if (a0 != (A)0) atomicAdd(&s[0], a0);
+    if (a1 != (A)0) atomicAdd(&s[1], a1);
+  }
+}
+
 template <typename A, int G>
 __global__ __launch_bounds__(256) void glm_csr_fwd_kernel(const long* __restrict__ indptr, const int* __restrict__ idx,
                                                           const A* __restrict__ val, const A* __restrict__ y,
@@ -108,9 +151,8 @@ __global__ __launch_bounds__(256) void glm_csr_fwd_kernel(const long* __restrict
   constexpr int K = G >= 32 ? 2 : 4;
   int e;
   if (!round_running(state, e)) return;
-  const long P = (n + B - 1) / B;
-  const long start = (long)(e % P) * B;
-  const long end = start + B < n ? start + B : n;
+  long start, end;
+  batch_rows(round_batch(e, n, B), n, B, start, end);
   const int lane = threadIdx.x & (G - 1);
   const long grp = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
   const long NG = ((long)gridDim.x * blockDim.x) / G;
@@ -144,21 +186,8 @@ __global__ __launch_bounds__(256) void glm_csr_fwd_kernel(const long* __restrict
     }
   }
   __shared__ A red[2][4];
-  wsum = wave_sum(wsum);
-  lsum = wave_sum(lsum);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[0][w] = wsum; red[1][w] = lsum; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    A a0 = 0, a1 = 0;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) { a0 += red[0][i]; a1 += red[1][i]; }
-    // one of WL_SLOTS cache lines per block: same-address float atomics from thousands of
-    // blocks serialise at the coherence point (measured: the single-address version cost more
-    // than the row math); the backward sums the slots in a fixed order
-    A* slot = wl + ((long)(e & 1) * WL_SLOTS + (blockIdx.x & (WL_SLOTS - 1))) * WL_STRIDE;
-    if (a0 != (A)0) atomicAdd(&slot[0], a0);
-    if (a1 != (A)0) atomicAdd(&slot[1], a1);
-  }
+  fwd_sums_stage(wave_sum(wsum), wave_sum(lsum), red);
+  fwd_sums_add(red, (int)(blockDim.x >> 6), wl, e, (int)blockIdx.x);
 }
 
 // Forward over row-block × column-split cells (BatchCsc cells, csc_build.hip cell_keys … cell_store):
@@ -189,10 +218,10 @@ __global__ __launch_bounds__(CELL_THREADS) void glm_csr_cell_fwd_kernel(
   __shared__ int sflag;
   int e;
   if (!round_running(state, e)) return;
-  const long P = (n + B - 1) / B;
-  const long b = (long)(e % P);
-  const long start = b * B;
-  const long blen = (start + B < n ? start + B : n) - start;
+  const long b = round_batch(e, n, B);
+  long start, end;
+  batch_rows(b, n, B, start, end);
+  const long blen = end - start;
   const int nrb = (int)((blen + RB - 1) >> rbb);
   const int ncell = nrb * S;
   int rb, sp;
@@ -291,23 +320,8 @@ __global__ __launch_bounds__(CELL_THREADS) void glm_csr_cell_fwd_kernel(
     ws += ww;
     ls += l;
   }
-  ws = wave_sum(ws);
-  ls = wave_sum(ls);
-  if ((tid & 63) == 0) {
-    red[0][tid >> 6] = ws;
-    red[1][tid >> 6] = ls;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    A a0 = 0, a1 = 0;
-    for (int i = 0; i < CELL_THREADS / 64; ++i) {
-      a0 += red[0][i];
-      a1 += red[1][i];
-    }
-    A* slot = wl + ((long)(e & 1) * WL_SLOTS + (rb & (WL_SLOTS - 1))) * WL_STRIDE;
-    if (a0 != (A)0) atomicAdd(&slot[0], a0);
-    if (a1 != (A)0) atomicAdd(&slot[1], a1);
-  }
+  fwd_sums_stage(wave_sum(ws), wave_sum(ls), red);
+  fwd_sums_add(red, CELL_THREADS / 64, wl, e, rb);
 }
 
 // Backward: a block owns 256 consecutive columns, whose batch entries are one contiguous CSC
@@ -329,6 +343,80 @@ __device__ __forceinline__ void slot_sums(const A* __restrict__ wl, int e, A& W,
   L = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
 }
 
+// The pieces the three backward kernels share (FUSE: the backward applies the update and the
+// termination check itself, 1 GPU; else it writes the feedback row fb[d + 2] for the all-reduce).
+//
+// Begin: block 0 re-arms the other parity's slots (they held the previous round's sums, consumed
+// by now); false when the round is not running (a fused backward still arrives: the state advances
+// once per launch).
+template <bool FUSE, typename A>
+__device__ __forceinline__ bool bwd_begin(int* __restrict__ state, A* __restrict__ wl, int& e) {
+  const bool run = round_running(state, e);
+  if (blockIdx.x == 0 && threadIdx.x < WL_SLOTS) {
+    A* o = wl + ((long)((e + 1) & 1) * WL_SLOTS + threadIdx.x) * WL_STRIDE;
+    o[0] = 0;
+    o[1] = 0;
+  }
+  if (!run && FUSE) arrive_and_advance(state, e, false, 0);
+  return run;
+}
+
+// Σweight of the round (batch b): the batch's row count when unweighted, else the fixed-order sum of
+// the forward's slots (identical in every block). Σloss only feeds the termination test, which the
+// last arriving block makes (bwd_finish), and block 0 of the feedback path, which exports it.
+template <bool FUSE, typename A>
+__device__ __forceinline__ void bwd_weights(const A* __restrict__ wl, int e, long b, long n, long B, int weighted, A& W,
+                                            A& L) {
+  L = 0;
+  if (weighted || (!FUSE && blockIdx.x == 0)) slot_sums(wl, e, W, L);
+  if (!weighted) {
+    long start, end;
+    batch_rows(b, n, B, start, end);
+    W = (A)(end - start);
+  }
+}
+
+// Column c's gradient sum g: the SGD step on its coefficient (w: its value before the step), or
+// its feedback entry.
+template <bool FUSE, typename A>
+__device__ __forceinline__ void put_col(A* __restrict__ coef, A* __restrict__ fb, long c, A w, A g, A W, A lr, A reg,
+                                        A en) {
+  if (FUSE)
+    coef[c] = sgd_apply<A>(w, g, W, lr, reg, en);
+  else
+    fb[c] = g;
+}
+template <bool FUSE, typename A>
+__device__ __forceinline__ void put_col(A* __restrict__ coef, A* __restrict__ fb, long c, A g, A W, A lr, A reg, A en) {
+  put_col<FUSE>(coef, fb, c, FUSE ? coef[c] : (A)0, g, W, lr, reg, en);
+}
+
+// the feedback row's Σweight / Σloss entries (block 0)
+template <bool FUSE, typename A>
+__device__ __forceinline__ void bwd_export(A* __restrict__ fb, int d, A W, A L) {
+  if (!FUSE && blockIdx.x == 0 && threadIdx.x == 0) {
+    fb[d] = W;
+    fb[d + 1] = L;
+  }
+}
+
+// The fused backward's last block (each kernel elects it its own way; every other block has
+// finished its reads of the state words by then, see arrive_and_advance): Σloss from the slots, the
+// termination test and the round state; `rearm`: the election drew ST_ARRIVE tickets.
+template <typename A>
+__device__ __forceinline__ void bwd_finish(int* __restrict__ state, const A* __restrict__ wl, int e, A W, int max_iter,
+                                           A tol, bool rearm) {
+  A w2, L;
+  slot_sums(wl, e, w2, L);
+  if (threadIdx.x == 0) {
+    const bool cont = (e + 1 < max_iter) && (L / W > tol);
+    state[ST_RUN0 + ((e + 1) & 1)] = cont ? 1 : 0;
+    state[ST_EXECUTED] += 1;
+    state[ST_ROUND] = e + 1;
+    if (rearm) state[ST_ARRIVE] = 0;
+  }
+}
+
 template <typename A, bool FUSE>
 __global__ __launch_bounds__(256) void glm_csc_bwd_kernel(const long* __restrict__ indptr,
                                                           const int* __restrict__ colptr, const int* __restrict__ erow,
@@ -338,34 +426,14 @@ __global__ __launch_bounds__(256) void glm_csc_bwd_kernel(const long* __restrict
                                                           int max_iter, A tol, A lr, A reg, A en, int weighted) {
   __shared__ A prod[CSC_CAP];
   int e;
-  const bool run = round_running(state, e);
-  // re-arm the other parity's slots (they held the previous round's sums, consumed by now)
-  if (blockIdx.x == 0) {
-    A* o = wl + ((long)((e + 1) & 1) * WL_SLOTS + threadIdx.x) * WL_STRIDE;
-    o[0] = 0;
-    o[1] = 0;
-  }
-  if (!run) {
-    if (FUSE) arrive_and_advance(state, e, false, 0);
-    return;
-  }
-  const long P = (n + B - 1) / B;
-  const long b = (long)(e % P);
+  if (!bwd_begin<FUSE>(state, wl, e)) return;
+  const long b = round_batch(e, n, B);
   const long base = indptr[b * B];
   const int* __restrict__ cp = colptr + b * (long)(d + 1);
   const int* __restrict__ er = erow + base;
   const A* __restrict__ ev = eval + base;
-  // Σweight of the round: the batch's row count when unweighted, else the fixed-order sum of the
-  // forward's slots (identical in every block). Σloss only feeds the termination test, which the
-  // last arriving block makes (and block 0 of the feedback path, which exports it).
-  A W, L = 0;
-  if (weighted || (!FUSE && blockIdx.x == 0)) {
-    slot_sums(wl, e, W, L);
-  }
-  if (!weighted) {
-    const long end = (b + 1) * B < n ? (b + 1) * B : n;
-    W = (A)(end - b * B);
-  }
+  A W, L;
+  bwd_weights<FUSE>(wl, e, b, n, B, weighted, W, L);
   for (int cb = blockIdx.x * 256; cb < d; cb += gridDim.x * 256) {
     const int c = cb + (int)threadIdx.x;
     const int ce = cb + 256 < d ? cb + 256 : d;
@@ -396,17 +464,9 @@ __global__ __launch_bounds__(256) void glm_csc_bwd_kernel(const long* __restrict
       for (int j = a; j < z; ++j) g += prod[j - pb];
       __syncthreads();
     }
-    if (c < d) {
-      if (FUSE)
-        coef[c] = sgd_apply<A>(coef[c], g, W, lr, reg, en);
-      else
-        fb[c] = g;
-    }
+    if (c < d) put_col<FUSE>(coef, fb, c, g, W, lr, reg, en);
   }
-  if (!FUSE && blockIdx.x == 0 && threadIdx.x == 0) {
-    fb[d] = W;
-    fb[d + 1] = L;
-  }
+  bwd_export<FUSE>(fb, d, W, L);
   if (FUSE) {
     __shared__ int last;
     __syncthreads();
@@ -414,17 +474,7 @@ __global__ __launch_bounds__(256) void glm_csc_bwd_kernel(const long* __restrict
       last = __hip_atomic_fetch_add(&state[ST_ARRIVE], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
              (int)gridDim.x - 1;
     __syncthreads();
-    if (last) {  // every other block has finished its reads of the state words (see arrive_and_advance)
-      A w2;
-      slot_sums(wl, e, w2, L);
-      if (threadIdx.x == 0) {
-        const bool cont = (e + 1 < max_iter) && (L / W > tol);
-        state[ST_RUN0 + ((e + 1) & 1)] = cont ? 1 : 0;
-        state[ST_EXECUTED] += 1;
-        state[ST_ROUND] = e + 1;
-        state[ST_ARRIVE] = 0;
-      }
-    }
+    if (last) bwd_finish(state, wl, e, W, max_iter, tol, true);
   }
 }
 
@@ -453,18 +503,8 @@ __global__ __launch_bounds__(TILE_THREADS) void glm_csc_tile_bwd_kernel(
   A* prod = reinterpret_cast<A*>(tile_smem);
   __shared__ A hred[TILE_THREADS / 64];
   int e;
-  const bool run = round_running(state, e);
-  if (blockIdx.x == 0 && threadIdx.x < WL_SLOTS) {
-    A* o = wl + ((long)((e + 1) & 1) * WL_SLOTS + threadIdx.x) * WL_STRIDE;
-    o[0] = 0;
-    o[1] = 0;
-  }
-  if (!run) {
-    if (FUSE) arrive_and_advance(state, e, false, 0);
-    return;
-  }
-  const long P = (n + B - 1) / B;
-  const long b = (long)(e % P);
+  if (!bwd_begin<FUSE>(state, wl, e)) return;
+  const long b = round_batch(e, n, B);
   const long base = indptr[b * B];
   const int* __restrict__ cp = colptr + b * (long)(d + 1);
   const int2* __restrict__ tl = tiles + b * (long)tstride;
@@ -472,12 +512,8 @@ __global__ __launch_bounds__(TILE_THREADS) void glm_csc_tile_bwd_kernel(
   const int* __restrict__ er = erow + base;
   const A* __restrict__ ev = eval + base;
   const uint32_t rmask = (1u << rb) - 1;
-  A W, L = 0;
-  if (weighted || (!FUSE && blockIdx.x == 0)) slot_sums(wl, e, W, L);
-  if (!weighted) {
-    const long end = (b + 1) * B < n ? (b + 1) * B : n;
-    W = (A)(end - b * B);
-  }
+  A W, L;
+  bwd_weights<FUSE>(wl, e, b, n, B, weighted, W, L);
   const int tid = threadIdx.x;
   for (int t = blockIdx.x; t < nt; t += gridDim.x) {
     const int2 ta = tl[t], tz = tl[t + 1];  // (start column, first entry) of this and the next tile
@@ -494,10 +530,7 @@ __global__ __launch_bounds__(TILE_THREADS) void glm_csc_tile_bwd_kernel(
       if (tid == 0) {
         A s = 0;
         for (int i = 0; i < TILE_THREADS / 64; ++i) s += hred[i];
-        if (FUSE)
-          coef[c0] = sgd_apply<A>(coef[c0], s, W, lr, reg, en);
-        else
-          fb[c0] = s;
+        put_col<FUSE>(coef, fb, c0, s, W, lr, reg, en);
       }
       __syncthreads();
       continue;
@@ -566,30 +599,19 @@ __global__ __launch_bounds__(TILE_THREADS) void glm_csc_tile_bwd_kernel(
         const int c = c0 + tid + i * TILE_THREADS;
         A g = 0;
         for (int j = ca[i] - k0; j < cz[i] - k0; ++j) g += prod[j];
-        if (c < c1) {
-          if (FUSE)
-            coef[c] = sgd_apply<A>(cw[i], g, W, lr, reg, en);
-          else
-            fb[c] = g;
-        }
+        if (c < c1) put_col<FUSE>(coef, fb, c, cw[i], g, W, lr, reg, en);
       }
     } else {
       for (int c = c0 + tid; c < c1; c += TILE_THREADS) {
         const int a = cp[c] - k0, z = cp[c + 1] - k0;
         A g = 0;
         for (int j = a; j < z; ++j) g += prod[j];
-        if (FUSE)
-          coef[c] = sgd_apply<A>(coef[c], g, W, lr, reg, en);
-        else
-          fb[c] = g;
+        put_col<FUSE>(coef, fb, c, g, W, lr, reg, en);
       }
     }
     __syncthreads();
   }
-  if (!FUSE && blockIdx.x == 0 && tid == 0) {
-    fb[d] = W;
-    fb[d + 1] = L;
-  }
+  bwd_export<FUSE>(fb, d, W, L);
   if (trace && tid == 0) trace[(long)blockIdx.x * 4 + 3] = (long long)__builtin_amdgcn_s_memrealtime();
   if (FUSE) {
     __shared__ int last;
@@ -598,17 +620,7 @@ __global__ __launch_bounds__(TILE_THREADS) void glm_csc_tile_bwd_kernel(
       last = __hip_atomic_fetch_add(&state[ST_ARRIVE], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
              (int)gridDim.x - 1;
     __syncthreads();
-    if (last) {
-      A w2;
-      slot_sums(wl, e, w2, L);
-      if (tid == 0) {
-        const bool cont = (e + 1 < max_iter) && (L / W > tol);
-        state[ST_RUN0 + ((e + 1) & 1)] = cont ? 1 : 0;
-        state[ST_EXECUTED] += 1;
-        state[ST_ROUND] = e + 1;
-        state[ST_ARRIVE] = 0;
-      }
-    }
+    if (last) bwd_finish(state, wl, e, W, max_iter, tol, true);
   }
 }
 
@@ -721,9 +733,7 @@ __device__ __forceinline__ int bk_exscan_array(const int* v, int* out, int m, in
 
 __device__ __forceinline__ bool bk_batch(const int* state, long n, long B, long& start, long& end, int& e) {
   if (!round_running(state, e)) return false;
-  const long P = (n + B - 1) / B;
-  start = (long)(e % P) * B;
-  end = start + B < n ? start + B : n;
+  batch_rows(round_batch(e, n, B), n, B, start, end);
   return true;
 }
 
@@ -1012,26 +1022,9 @@ __global__ __launch_bounds__(SC_NT) void glm_bkt_fwd_scatter_kernel(
     wsum += ww;
     lsum += l;
   }
-  wsum = wave_sum(wsum);
-  lsum = wave_sum(lsum);
-  if ((tid & 63) == 0) {
-    red[0][tid >> 6] = wsum;
-    red[1][tid >> 6] = lsum;
-  }
-  __syncthreads();
+  fwd_sums_stage(wave_sum(wsum), wave_sum(lsum), red);
   BK_STAMP(3)
-  if (tid == 0) {
-    A a0 = 0, a1 = 0;
-#pragma unroll
-    for (int i = 0; i < SC_NT / 64; ++i) {
-      a0 += red[0][i];
-      a1 += red[1][i];
-    }
-    // one of WL_SLOTS cache lines per block (same-address atomics from every block serialise)
-    A* ws = wl + ((long)(e & 1) * WL_SLOTS + (blockIdx.x & (WL_SLOTS - 1))) * WL_STRIDE;
-    if (a0 != (A)0) atomicAdd(&ws[0], a0);
-    if (a1 != (A)0) atomicAdd(&ws[1], a1);
-  }
+  fwd_sums_add(red, SC_NT / 64, wl, e, (int)blockIdx.x);
   if (one) {
     // a returning integer atomic on its bucket's cursor gives each entry its staging slot (the
     // products' staging values were consumed by the row dots before the last barrier)
@@ -1116,24 +1109,10 @@ __global__ __launch_bounds__(BK_NT) void glm_bkt_bwd_kernel(const long* __restri
   __shared__ int tmp[BK_NT / 64];
   __shared__ int sflag;
   int e;
-  const bool run = round_running(state, e);
-  if (blockIdx.x == 0 && threadIdx.x < WL_SLOTS) {  // re-arm the other parity's Σw/Σloss slots
-    A* o = wl + ((long)((e + 1) & 1) * WL_SLOTS + threadIdx.x) * WL_STRIDE;
-    o[0] = 0;
-    o[1] = 0;
-  }
-  if (!run) {
-    if (FUSE) arrive_and_advance(state, e, false, 0);
-    return;
-  }
-  const long P = (n + B - 1) / B;
-  const long b = (long)(e % P);
-  A W, L = 0;
-  if (weighted || (!FUSE && blockIdx.x == 0)) slot_sums(wl, e, W, L);
-  if (!weighted) {
-    const long end = (b + 1) * B < n ? (b + 1) * B : n;
-    W = (A)(end - b * B);
-  }
+  if (!bwd_begin<FUSE>(state, wl, e)) return;
+  const long b = round_batch(e, n, B);
+  A W, L;
+  bwd_weights<FUSE>(wl, e, b, n, B, weighted, W, L);
   // bucket starts, then the work items: chunks of `chunk` entries of each bucket (at least one per
   // bucket: every column is updated, regularisation included)
   const long sl = bk_slot(e, n, B, k);
@@ -1208,10 +1187,7 @@ __global__ __launch_bounds__(BK_NT) void glm_bkt_bwd_kernel(const long* __restri
         const int j0 = c ? cc[c - 1] : 0, j1 = cc[c];
         A g = 0;
         for (int j = j0; j < j1; ++j) g += sv[j];
-        if (FUSE)
-          coef[c0 + c] = sgd_apply<A>(wold[u], g, W, lr, reg, en);
-        else
-          fb[c0 + c] = g;
+        put_col<FUSE>(coef, fb, c0 + c, wold[u], g, W, lr, reg, en);
       }
     } else {
       for (int c = threadIdx.x; c < cols; c += BK_NT) {
@@ -1223,20 +1199,14 @@ __global__ __launch_bounds__(BK_NT) void glm_bkt_bwd_kernel(const long* __restri
       if (arrive_last(&k.done[bk], nc, &sflag)) {
         for (int c = threadIdx.x; c < cols; c += BK_NT) {
           const A g = __hip_atomic_exchange(&acc[c0 + c], (A)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (FUSE)
-            coef[c0 + c] = sgd_apply<A>(coef[c0 + c], g, W, lr, reg, en);
-          else
-            fb[c0 + c] = g;
+          put_col<FUSE>(coef, fb, c0 + c, g, W, lr, reg, en);
         }
         if (threadIdx.x == 0) st_agent(&k.done[bk], 0);
       }
     }
     __syncthreads();
   }
-  if (!FUSE && blockIdx.x == 0 && threadIdx.x == 0) {
-    fb[d] = W;
-    fb[d + 1] = L;
-  }
+  bwd_export<FUSE>(fb, d, W, L);
   if (FUSE) {
     // two-level arrival (a single counter serialises every block's ticket, ~11 ns each): the last
     // block of each group of blocks ≡ g (mod 8) draws a top ticket; the last top one finishes
@@ -1256,17 +1226,26 @@ __global__ __launch_bounds__(BK_NT) void glm_bkt_bwd_kernel(const long* __restri
       last = top;
     }
     __syncthreads();
-    if (last) {  // every other block has finished its reads of the state words
-      A w2;
-      slot_sums(wl, e, w2, L);
-      if (threadIdx.x == 0) {
-        const bool cont = (e + 1 < max_iter) && (L / W > tol);
-        state[ST_RUN0 + ((e + 1) & 1)] = cont ? 1 : 0;
-        state[ST_EXECUTED] += 1;
-        state[ST_ROUND] = e + 1;
-      }
-    }
+    if (last) bwd_finish(state, wl, e, W, max_iter, tol, false);
   }
+}
+
+// the launch variants' visitors (the accumulator type: with_acc, glm_core.h): f is called with the
+// lane-group size / the flag as a compile-time constant; −1 for a group size no kernel has
+template <typename F>
+int with_group(int G, F&& f) {
+  switch (G) {
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 32: return f(std::integral_constant<int, 32>{});
+    case 64: return f(std::integral_constant<int, 64>{});
+    default: return -1;
+  }
+}
+template <typename F>
+int with_flag(int on, F&& f) {
+  return on ? f(std::true_type{}) : f(std::false_type{});
 }
 
 }  // namespace
@@ -1284,18 +1263,16 @@ FMLX_API void fmlx_glm_bkt_set_trace(void* trace, long blocks) {
 FMLX_API int fmlx_glm_grad_csr(int acc_f64, const long* indptr, const int* idx, const void* val, const void* y,
                                const void* wt, const void* coef, long n, int d, long B, int loss, const int* state,
                                void* grad, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
   long waves = B < n ? B : n;
   int blocks = (int)((waves + 3) / 4);
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
-  if (acc_f64)
-    hipLaunchKernelGGL(glm_grad_csr_kernel<double>, dim3(blocks), dim3(256), 0, s, indptr, idx, (const double*)val,
-                       (const double*)y, (const double*)wt, (const double*)coef, n, d, B, loss, state, (double*)grad);
-  else
-    hipLaunchKernelGGL(glm_grad_csr_kernel<float>, dim3(blocks), dim3(256), 0, s, indptr, idx, (const float*)val,
-                       (const float*)y, (const float*)wt, (const float*)coef, n, d, B, loss, state, (float*)grad);
-  return (int)hipGetLastError();
+  return with_acc(acc_f64, [&](auto acc) {
+    typedef decltype(acc) A;
+    hipLaunchKernelGGL(glm_grad_csr_kernel<A>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, indptr, idx,
+                       (const A*)val, (const A*)y, (const A*)wt, (const A*)coef, n, d, B, loss, state, (A*)grad);
+    return (int)hipGetLastError();
+  });
 }
 
 static int g_csc_fwd_cap = 65535, g_csc_bwd_cap = 1024, g_csc_tile_cap = 0;  // 0: CUs × tile blocks per CU
@@ -1305,6 +1282,22 @@ FMLX_API void fmlx_glm_set_csc_tuning(int fwd_cap, int bwd_cap) {
   g_csc_bwd_cap = bwd_cap > 0 ? bwd_cap : 1024;
   g_csc_tile_cap = bwd_cap > 0 ? bwd_cap : 0;
 }
+
+// what both round entry points take: the CSR partition, the model and the round's parameters
+struct SparseRound {
+  const long* indptr;
+  const int* idx;
+  const void *val, *y, *wt;
+  void* coef;
+  long n;
+  int d;
+  long B;
+  int loss;
+  int* state;
+  void *wl, *fb;
+  int fuse, max_iter;
+  double tol, lr, reg, en;
+};
 
 // tiled backward: the column tiles of the batches (BatchCsc.tiles) and the packing of erow
 // forward cells in XCD-aware order (default; fmlx_glm_set_cell_xcd(0): launch order) — 63.5 → 61.4 µs
@@ -1325,78 +1318,53 @@ struct CscTiles {
 };
 FMLX_API int fmlx_glm_wl_elems() { return 2 * WL_SLOTS * WL_STRIDE; }
 
+// the transposed round's two launches: forward (cells, or a G-lane group per row), backward (tiled or not)
 template <typename A, int G>
-static void launch_csc_round(const long* indptr, const int* idx, const A* val, const A* y, const A* wt, A* coef,
-                             long n, int d, long B, int loss, int* state, A* mult, A* wl, const int* colptr,
-                             const int* erow, const A* eval, A* fb, int fuse, int max_iter, A tol, A lr, A reg, A en,
-                             const CscTiles& ti, hipStream_t s) {
+static int launch_csc_round(const SparseRound& r, void* mult, const int* colptr, const int* erow, const void* eval,
+                            const CscTiles& ti, hipStream_t s) {
   if (ti.cent != nullptr) {
     hipLaunchKernelGGL(glm_csr_cell_fwd_kernel<A>, dim3(ti.cells), dim3(CELL_THREADS), (size_t)ti.cmax * sizeof(A),
-                       s, indptr, ti.cent, (const A*)ti.cval, ti.roff, (long)ti.rstride, ti.rbb, ti.S, ti.CS, ti.cb, y, wt,
-                       (const A*)coef, n, B, loss, state, mult, wl, (A*)ti.partial, ti.cnt, g_cell_xcd);
+                       s, r.indptr, ti.cent, (const A*)ti.cval, ti.roff, (long)ti.rstride, ti.rbb, ti.S, ti.CS, ti.cb,
+                       (const A*)r.y, (const A*)r.wt, (const A*)r.coef, r.n, r.B, r.loss, r.state, (A*)mult, (A*)r.wl,
+                       (A*)ti.partial, ti.cnt, g_cell_xcd);
   } else {
-    const long groups = B < n ? B : n;
+    const long groups = r.B < r.n ? r.B : r.n;
     long fb_blocks = (groups * G + 255) / 256;  // one row per lane group: the batch in one pass
     if (fb_blocks > g_csc_fwd_cap) fb_blocks = g_csc_fwd_cap;
     if (fb_blocks < 1) fb_blocks = 1;
-    hipLaunchKernelGGL((glm_csr_fwd_kernel<A, G>), dim3((int)fb_blocks), dim3(256), 0, s, indptr, idx, val, y, wt,
-                       (const A*)coef, n, B, loss, state, mult, wl);
+    hipLaunchKernelGGL((glm_csr_fwd_kernel<A, G>), dim3((int)fb_blocks), dim3(256), 0, s, r.indptr, r.idx,
+                       (const A*)r.val, (const A*)r.y, (const A*)r.wt, (const A*)r.coef, r.n, r.B, r.loss, r.state,
+                       (A*)mult, (A*)r.wl);
   }
-  const int weighted = wt != nullptr;
-  if (ti.tiles != nullptr) {
-    const size_t lds = (size_t)ti.ET * sizeof(A);
-    int per_cu = (int)(LDS_PER_CU / (lds + 2048));
-    per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);  // ≤ 32 waves per CU at 1024 threads
-    int tb = g_csc_tile_cap > 0 ? g_csc_tile_cap : NUM_CU * per_cu;
-    if (tb > ti.tstride) tb = ti.tstride;
-#define FMLX_TILE_BWD(F)                                                                                             \
-  hipLaunchKernelGGL((glm_csc_tile_bwd_kernel<A, F>), dim3(tb), dim3(TILE_THREADS), lds, s, indptr, colptr, ti.tiles, \
-                     ti.ntiles, ti.tstride, erow, eval, (const A*)mult, n, d, B, ti.rb, ti.EL, state, wl, fb, coef,    \
-                     max_iter, tol, lr, reg, en, weighted, g_sparse_trace)
-    if (fuse)
-      FMLX_TILE_BWD(true);
-    else
-      FMLX_TILE_BWD(false);
-#undef FMLX_TILE_BWD
-    return;
-  }
-  int bb = (d + 255) / 256;  // grid-strided: each block takes the arrival ticket once
-  if (bb > g_csc_bwd_cap) bb = g_csc_bwd_cap;
-  if (fuse)
-    hipLaunchKernelGGL((glm_csc_bwd_kernel<A, true>), dim3(bb), dim3(256), 0, s, indptr, colptr, erow, eval,
-                       (const A*)mult, n, d, B, state, wl, fb, coef, max_iter, tol, lr, reg, en, weighted);
-  else
-    hipLaunchKernelGGL((glm_csc_bwd_kernel<A, false>), dim3(bb), dim3(256), 0, s, indptr, colptr, erow, eval,
-                       (const A*)mult, n, d, B, state, wl, fb, coef, max_iter, tol, lr, reg, en, weighted);
+  const int weighted = r.wt != nullptr;
+  return with_flag(r.fuse, [&](auto fuse) {
+    constexpr bool F = decltype(fuse)::value;
+    if (ti.tiles != nullptr) {
+      const size_t lds = (size_t)ti.ET * sizeof(A);
+      int per_cu = (int)(LDS_PER_CU / (lds + 2048));
+      per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);  // ≤ 32 waves per CU at 1024 threads
+      int tb = g_csc_tile_cap > 0 ? g_csc_tile_cap : NUM_CU * per_cu;
+      if (tb > ti.tstride) tb = ti.tstride;
+      hipLaunchKernelGGL((glm_csc_tile_bwd_kernel<A, F>), dim3(tb), dim3(TILE_THREADS), lds, s, r.indptr, colptr,
+                         ti.tiles, ti.ntiles, ti.tstride, erow, (const A*)eval, (const A*)mult, r.n, r.d, r.B, ti.rb,
+                         ti.EL, r.state, (A*)r.wl, (A*)r.fb, (A*)r.coef, r.max_iter, (A)r.tol, (A)r.lr, (A)r.reg,
+                         (A)r.en, weighted, g_sparse_trace);
+    } else {
+      int bb = (r.d + 255) / 256;  // grid-strided: each block takes the arrival ticket once
+      if (bb > g_csc_bwd_cap) bb = g_csc_bwd_cap;
+      hipLaunchKernelGGL((glm_csc_bwd_kernel<A, F>), dim3(bb), dim3(256), 0, s, r.indptr, colptr, erow,
+                         (const A*)eval, (const A*)mult, r.n, r.d, r.B, r.state, (A*)r.wl, (A*)r.fb, (A*)r.coef,
+                         r.max_iter, (A)r.tol, (A)r.lr, (A)r.reg, (A)r.en, weighted);
+    }
+    return (int)hipGetLastError();
+  });
 }
 
-template <typename A>
-static int dispatch_csc_round(int G, const long* indptr, const int* idx, const void* val, const void* y,
-                              const void* wt, void* coef, long n, int d, long B, int loss, int* state, void* mult,
-                              void* wl, const int* colptr, const int* erow, const void* eval, void* fb, int fuse,
-                              int max_iter, double tol, double lr, double reg, double en, const CscTiles& ti,
-                              hipStream_t s) {
-#define FMLX_CSC(GG)                                                                                                 \
-  launch_csc_round<A, GG>(indptr, idx, (const A*)val, (const A*)y, (const A*)wt, (A*)coef, n, d, B, loss, state,     \
-                          (A*)mult, (A*)wl, colptr, erow, (const A*)eval, (A*)fb, fuse, max_iter, (A)tol, (A)lr,     \
-                          (A)reg, (A)en, ti, s)
-  switch (G) {
-    case 4: FMLX_CSC(4); break;
-    case 8: FMLX_CSC(8); break;
-    case 16: FMLX_CSC(16); break;
-    case 32: FMLX_CSC(32); break;
-    case 64: FMLX_CSC(64); break;
-    default: return -1;
-  }
-#undef FMLX_CSC
-  return (int)hipGetLastError();
-}
+FMLX_API void fmlx_glm_set_cell_xcd(int on) { g_cell_xcd = on != 0; }
 
 // One sparse SGD round through the per-batch transpose (see glm_csc_bwd_kernel). fuse=1: the
 // backward applies the update + termination (1 GPU); fuse=0: it writes fb[d+2] for the
 // all-reduce and fmlx_glm_update follows.
-FMLX_API void fmlx_glm_set_cell_xcd(int on) { g_cell_xcd = on != 0; }
-
 FMLX_API int fmlx_glm_csc_round(int acc_f64, int G, const long* indptr, const int* idx, const void* val,
                                 const void* y, const void* wt, void* coef, long n, int d, long B, int loss, int* state,
                                 void* mult, void* wl, const int* colptr, const int* erow, const void* eval, void* fb,
@@ -1414,7 +1382,7 @@ FMLX_API int fmlx_glm_csc_round(int acc_f64, int G, const long* indptr, const in
     if (cval == nullptr || roff == nullptr || partial == nullptr || ccnt == nullptr || S < 1 || CS < 1 || cb < 1 ||
         cb >= 32 || rbb < 1 || rbb > CELL_RBB_MAX || cells < 1 || (long)rstride < ((long)cells << rbb) + 1 ||
         (long)CS * S < d || cmax < 0 ||
-        cmax > (int)(1u << (32 - cb)) || lds > 150 * 1024)
+        (long)cmax > (1L << (32 - cb)) || lds > 150 * 1024)  // (64-bit: cb = 1 allows 2^31 ranks)
       return -5;
   }
   if (tiles != nullptr) {
@@ -1423,26 +1391,25 @@ FMLX_API int fmlx_glm_csc_round(int acc_f64, int G, const long* indptr, const in
     if (rb < 1 || ET < 2 || EL < 1 || EL >= ET || tstride < 2 || (size_t)ET * esz > (size_t)LDS_PER_CU - 1024) return -3;
     if (((long)ET - 1) >> (32 - rb) != 0 || (B - 1) >> rb != 0) return -4;
   }
-  if (acc_f64)
-    return dispatch_csc_round<double>(G, indptr, idx, val, y, wt, coef, n, d, B, loss, state, mult, wl, colptr, erow,
-                                      eval, fb, fuse, max_iter, tol, lr, reg, en, ti, s);
-  return dispatch_csc_round<float>(G, indptr, idx, val, y, wt, coef, n, d, B, loss, state, mult, wl, colptr, erow,
-                                   eval, fb, fuse, max_iter, tol, lr, reg, en, ti, s);
+  const SparseRound r{indptr, idx, val, y, wt, coef, n, d, B, loss, state, wl, fb, fuse, max_iter, tol, lr, reg, en};
+  return with_acc(acc_f64, [&](auto acc) {
+    return with_group(G, [&](auto g) {
+      return launch_csc_round<decltype(acc), decltype(g)::value>(r, mult, colptr, erow, eval, ti, s);
+    });
+  });
 }
 
 FMLX_API int fmlx_glm_csr_predict(int acc_f64, const long* indptr, const int* idx, const void* val, const void* coef,
                                   long n, double* dots, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
   if (n == 0) return 0;
   int blocks = (int)((n + 3) / 4);
   if (blocks > 4096) blocks = 4096;
-  if (acc_f64)
-    hipLaunchKernelGGL(glm_csr_predict_kernel<double>, dim3(blocks), dim3(256), 0, s, indptr, idx, (const double*)val,
-                       (const double*)coef, n, dots);
-  else
-    hipLaunchKernelGGL(glm_csr_predict_kernel<float>, dim3(blocks), dim3(256), 0, s, indptr, idx, (const float*)val,
-                       (const float*)coef, n, dots);
-  return (int)hipGetLastError();
+  return with_acc(acc_f64, [&](auto acc) {
+    typedef decltype(acc) A;
+    hipLaunchKernelGGL(glm_csr_predict_kernel<A>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, indptr, idx,
+                       (const A*)val, (const A*)coef, n, dots);
+    return (int)hipGetLastError();
+  });
 }
 
 // ---- single-visit bucket round (glm_bkt_*) ----
@@ -1467,30 +1434,34 @@ static size_t bkt_fwd_lds(const BktArgs& k, size_t es) {
          (size_t)(es == 8 ? bk_ecap<double>() : bk_ecap<float>()) * (4 + es + 2);
 }
 
+// the backward's LDS: the chunk's values, a counter per slice column (+ 1), bst / iofs [nb + 1], nch [nb]
+static size_t bkt_bwd_lds(const BktArgs& k, size_t es) {
+  return (size_t)k.chunk * es + (((size_t)1 << k.csb) + 1 + 3 * (size_t)k.nb + 2) * 4;
+}
+
+// the bucket round's launches: count + scan + base of the round's batch unless the fit counted its
+// batches once (k.slots), forward + scatter, backward
 template <typename A, int G>
-static void launch_bkt_round(const long* indptr, const int* idx, const A* val, const A* y, const A* wt, A* coef,
-                             long n, int d, long B, int loss, int* state, A* wl, A* fb, int fuse,
-                             int max_iter, A tol, A lr, A reg, A en, const BktArgs& k, int bwd_blocks, hipStream_t s) {
-  const long rows = B < n ? B : n;
+static int launch_bkt_round(const SparseRound& r, const BktArgs& k, int bwd_blocks, hipStream_t s) {
+  const long rows = r.B < r.n ? r.B : r.n;
   const int fblocks = (int)((rows + k.rb - 1) / k.rb);
   if (!k.slots) {
     hipLaunchKernelGGL(glm_bkt_count_kernel, dim3((fblocks + CG - 1) / CG), dim3(BK_NT), (size_t)CG * k.nb * 4, s,
-                       indptr, idx, n, B, state, k);
-    hipLaunchKernelGGL(glm_bkt_scan_kernel, dim3(k.nb), dim3(BK_NT), 0, s, n, B, state, k);
+                       r.indptr, r.idx, r.n, r.B, r.state, k);
+    hipLaunchKernelGGL(glm_bkt_scan_kernel, dim3(k.nb), dim3(BK_NT), 0, s, r.n, r.B, r.state, k);
     hipLaunchKernelGGL(glm_bkt_base_kernel, dim3(bkt_base_blocks(fblocks, k.nb)), dim3(BK_NT),
-                       (size_t)(k.nb + 1) * 4, s, n, B, state, k);
+                       (size_t)(k.nb + 1) * 4, s, r.n, r.B, r.state, k);
   }
   hipLaunchKernelGGL((glm_bkt_fwd_scatter_kernel<A, G>), dim3(fblocks), dim3(SC_NT), bkt_fwd_lds(k, sizeof(A)), s,
-                     indptr, idx, val, y, wt, (const A*)coef, n, B, loss, state, wl, k, g_bkt_trace, g_bkt_trace_blocks);
-  const size_t blds = (size_t)k.chunk * sizeof(A) + (((size_t)1 << k.csb) + 1 + 3 * (size_t)k.nb + 2) * 4;
-  const int weighted = wt != nullptr;
-  if (blds > (size_t)LDS_PER_CU) return;  // (fmlx_glm_bkt_round checks it first)
-  if (fuse)
-    hipLaunchKernelGGL((glm_bkt_bwd_kernel<A, true>), dim3(bwd_blocks), dim3(BK_NT), blds, s, indptr, n, d, B, state,
-                       wl, fb, coef, max_iter, tol, lr, reg, en, weighted, k);
-  else
-    hipLaunchKernelGGL((glm_bkt_bwd_kernel<A, false>), dim3(bwd_blocks), dim3(BK_NT), blds, s, indptr, n, d, B, state,
-                       wl, fb, coef, max_iter, tol, lr, reg, en, weighted, k);
+                     r.indptr, r.idx, (const A*)r.val, (const A*)r.y, (const A*)r.wt, (const A*)r.coef, r.n, r.B,
+                     r.loss, r.state, (A*)r.wl, k, g_bkt_trace, g_bkt_trace_blocks);
+  const int weighted = r.wt != nullptr;
+  return with_flag(r.fuse, [&](auto fuse) {
+    hipLaunchKernelGGL((glm_bkt_bwd_kernel<A, decltype(fuse)::value>), dim3(bwd_blocks), dim3(BK_NT),
+                       bkt_bwd_lds(k, sizeof(A)), s, r.indptr, r.n, r.d, r.B, r.state, (A*)r.wl, (A*)r.fb, (A*)r.coef,
+                       r.max_iter, (A)r.tol, (A)r.lr, (A)r.reg, (A)r.en, weighted, k);
+    return (int)hipGetLastError();
+  });
 }
 
 // The fit's one-time counts: count + scan of batches 0 … slots − 1 of the partition in two launches
@@ -1532,35 +1503,22 @@ FMLX_API int fmlx_glm_bkt_round(int acc_f64, int G, const long* indptr, const in
   if (nb > BK_NB_MAX || rb < 1 || rb > 4096 || chunk < BK_NT || bwd_blocks < 1)
     return -4;
   if (chunk > (acc_f64 ? bk_chunk<double>() : bk_chunk<float>()) || csb > 12) return -6;
-  if ((size_t)chunk * es + (((size_t)1 << csb) + 1 + 3 * (size_t)nb + 2) * 4 > (size_t)LDS_PER_CU) return -7;
-  if (slots < 0 || mstride < fblocks * nb) return -8;
   const BktArgs k{csb, (int)nb, rb, chunk, cntm, offm, lofs, tot, bst, slots, mstride, done, rec, acc};
+  if (bkt_bwd_lds(k, es) > (size_t)LDS_PER_CU) return -7;
+  if (slots < 0 || mstride < fblocks * nb) return -8;
   if (bkt_fwd_lds(k, es) > (size_t)LDS_PER_CU / 2) return -5;
-#define FMLX_BKT(GG)                                                                                                  \
-  if (acc_f64)                                                                                                        \
-    launch_bkt_round<double, GG>(indptr, idx, (const double*)val, (const double*)y, (const double*)wt, (double*)coef,  \
-                                 n, d, B, loss, state, (double*)wl, (double*)fb, fuse, max_iter, tol,  \
-                                 lr, reg, en, k, bwd_blocks, s);                                                                      \
-  else                                                                                                                \
-    launch_bkt_round<float, GG>(indptr, idx, (const float*)val, (const float*)y, (const float*)wt, (float*)coef, n, d, \
-                                B, loss, state, (float*)wl, (float*)fb, fuse, max_iter, (float)tol,     \
-                                (float)lr, (float)reg, (float)en, k, bwd_blocks, s);
-  switch (G) {
-    case 4: FMLX_BKT(4); break;
-    case 8: FMLX_BKT(8); break;
-    case 16: FMLX_BKT(16); break;
-    case 32: FMLX_BKT(32); break;
-    case 64: FMLX_BKT(64); break;
-    default: return -1;
-  }
-#undef FMLX_BKT
-  return (int)hipGetLastError();
+  const SparseRound r{indptr, idx, val, y, wt, coef, n, d, B, loss, state, wl, fb, fuse, max_iter, tol, lr, reg, en};
+  return with_acc(acc_f64, [&](auto a) {
+    return with_group(G, [&](auto g) {
+      return launch_bkt_round<decltype(a), decltype(g)::value>(r, k, bwd_blocks, s);
+    });
+  });
 }
 
-// One dry launch of every sparse-round kernel (all variants) on a round state whose running flags
-// are 0, so each exits at its first check: the first launch of a kernel symbol pays a one-time
-// runtime cost (argument layout, dispatch set-up), which then falls at library load instead of
-// inside the first fit (the reference's totalTimeMs is a cold job).
+// One dry launch of every bucket-round and row-group forward kernel (all variants) on a round state
+// whose running flags are 0, so each exits at its first check: the first launch of a kernel symbol
+// pays a one-time runtime cost (argument layout, dispatch set-up), which then falls at library load
+// instead of inside the first fit (the reference's totalTimeMs is a cold job).
 FMLX_API int fmlx_glm_sparse_warm(void* stream) {
   hipStream_t s = (hipStream_t)stream;
   // [state | 4 KiB scratch | the Σw/Σloss slots the backward re-arms before its running check]
@@ -1580,24 +1538,27 @@ FMLX_API int fmlx_glm_sparse_warm(void* stream) {
   hipLaunchKernelGGL(glm_bkt_count_kernel, dim3(1), dim3(BK_NT), (size_t)CG * 4, s, ip, ix, 1L, 1L, (const int*)st, k);
   hipLaunchKernelGGL(glm_bkt_scan_kernel, dim3(1), dim3(BK_NT), 0, s, 1L, 1L, (const int*)st, k);
   hipLaunchKernelGGL(glm_bkt_base_kernel, dim3(1), dim3(BK_NT), 8, s, 1L, 1L, (const int*)st, k);
-#define FMLX_WARM(A, GG)                                                                                           \
-  hipLaunchKernelGGL((glm_csr_fwd_kernel<A, GG>), dim3(1), dim3(256), 0, s, ip, ix, (const A*)scratch,              \
-                     (const A*)scratch, (const A*)nullptr, (const A*)scratch, 1L, 1L, 1, (const int*)st, (A*)scratch, \
-                     (A*)scratch);                                                                                 \
-  hipLaunchKernelGGL((glm_bkt_fwd_scatter_kernel<A, GG>), dim3(1), dim3(SC_NT), 4096, s, ip, ix, (const A*)scratch, \
-                     (const A*)scratch, (const A*)nullptr, (const A*)scratch, 1L, 1L, 1, (const int*)st, (A*)wls, k,      \
-                     (long long*)nullptr, 0L);
-  FMLX_WARM(float, 4) FMLX_WARM(float, 8) FMLX_WARM(float, 16) FMLX_WARM(float, 32) FMLX_WARM(float, 64)
-  FMLX_WARM(double, 4) FMLX_WARM(double, 8) FMLX_WARM(double, 16) FMLX_WARM(double, 32) FMLX_WARM(double, 64)
-#undef FMLX_WARM
-  hipLaunchKernelGGL((glm_bkt_bwd_kernel<float, true>), dim3(1), dim3(BK_NT), 1024, s, ip, 1L, 1, 1L, st,
-                     (float*)wls, (float*)scratch, (float*)scratch, 1, 0.f, 0.f, 0.f, 0.f, 0, k);
-  hipLaunchKernelGGL((glm_bkt_bwd_kernel<float, false>), dim3(1), dim3(BK_NT), 1024, s, ip, 1L, 1, 1L, st,
-                     (float*)wls, (float*)scratch, (float*)scratch, 1, 0.f, 0.f, 0.f, 0.f, 0, k);
-  hipLaunchKernelGGL((glm_bkt_bwd_kernel<double, true>), dim3(1), dim3(BK_NT), 1024, s, ip, 1L, 1, 1L, st,
-                     (double*)wls, (double*)scratch, (double*)scratch, 1, 0.0, 0.0, 0.0, 0.0, 0, k);
-  hipLaunchKernelGGL((glm_bkt_bwd_kernel<double, false>), dim3(1), dim3(BK_NT), 1024, s, ip, 1L, 1, 1L, st,
-                     (double*)wls, (double*)scratch, (double*)scratch, 1, 0.0, 0.0, 0.0, 0.0, 0, k);
+  for (int f64 = 0; f64 < 2; ++f64)
+    with_acc(f64, [&](auto acc) {
+      typedef decltype(acc) A;
+      for (int G = 4; G <= 64; G *= 2)
+        with_group(G, [&](auto g) {
+          hipLaunchKernelGGL((glm_csr_fwd_kernel<A, decltype(g)::value>), dim3(1), dim3(256), 0, s, ip, ix,
+                             (const A*)scratch, (const A*)scratch, (const A*)nullptr, (const A*)scratch, 1L, 1L, 1,
+                             (const int*)st, (A*)scratch, (A*)scratch);
+          hipLaunchKernelGGL((glm_bkt_fwd_scatter_kernel<A, decltype(g)::value>), dim3(1), dim3(SC_NT), 4096, s, ip,
+                             ix, (const A*)scratch, (const A*)scratch, (const A*)nullptr, (const A*)scratch, 1L, 1L, 1,
+                             (const int*)st, (A*)wls, k, (long long*)nullptr, 0L);
+          return 0;
+        });
+      for (int fuse = 0; fuse < 2; ++fuse)
+        with_flag(fuse, [&](auto f) {
+          hipLaunchKernelGGL((glm_bkt_bwd_kernel<A, decltype(f)::value>), dim3(1), dim3(BK_NT), 1024, s, ip, 1L, 1, 1L,
+                             st, (A*)wls, (A*)scratch, (A*)scratch, 1, (A)0, (A)0, (A)0, (A)0, 0, k);
+          return 0;
+        });
+      return 0;
+    });
   return (int)hipGetLastError();
 }
 

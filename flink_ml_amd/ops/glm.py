@@ -321,7 +321,7 @@ def grad_csr(indptr, idx, val, y, wt, coef, n, d, B, loss, state, grad) -> None:
                 native.ptr(state), native.ptr(grad), native.stream_ptr(val.device))
 
 
-# sparse rounds through per-batch transposes (csrc/glm.hip glm_csc_bwd_kernel)
+# sparse rounds through per-batch transposes (csrc/glm_sparse.hip glm_csc_bwd_kernel)
 CSC_MAX_BYTES = 8 << 30  # the column-major copies of a partition: at most this much
 CSC_RUN_MAX = 16  # consecutive batches transposed per sort
 TRANSPOSE = True  # False: the transposed layout is never built (the atomic-scatter fallback; tests)
@@ -470,7 +470,7 @@ TILE_MIN_VISITS = 16
 # (BucketRound) instead of any per-batch transpose; BUCKETS = False: the transposed rounds (tests)
 BUCKETS = True
 TILE_SPREAD = True  # tile size from the batch and CU count
-# the forward over row-block × column-split cells (glm.hip glm_csr_cell_fwd_kernel): float atomics
+# the forward over row-block × column-split cells (glm_sparse.hip glm_csr_cell_fwd_kernel): float atomics
 # in LDS, so off under FMLX_DETERMINISTIC=1 (the one-row-per-lane-group forward is bit-stable)
 CELLS = True
 CELL_RBB = None  # rows per row block 2^this ≤ 2^11 (None: 10 or 11, by the cell shape rules)
@@ -525,7 +525,7 @@ class BatchCsc:
         self._want = max(1, min(cap, self.P))
         self.colptr = self.erow = self.evals = None
         self.version = 0
-        # row-sorted column tiles (glm.hip glm_csc_tile_bwd_kernel; CUDA partitions only)
+        # row-sorted column tiles (glm_sparse.hip glm_csc_tile_bwd_kernel; CUDA partitions only)
         self.ET = csc_tile_entries(B, values.dtype == torch.float64) if values.device.type == "cuda" else 0
         # a column of more than EL entries is a tile of its own (block-strided sum); light tiles
         # start inside one EB-entry bucket, so they hold ≤ EB + EL = ET entries (≈ EB on average)
@@ -548,6 +548,7 @@ class BatchCsc:
         # column-sorted per cell, packed (column − s·CS) | row-major rank << cb; roff: first entry
         # of every (cell, row); cmax: entries of the largest built cell (the kernel's LDS slots)
         self.cells = self.cmax = 0
+        self.S = self.CS = self.cb = 0  # (no cells: the row-group forward)
         self.rbb = max(1, min(11, CELL_RBB or 10))  # (_pick_cells)
         self.cent = self.cval = self.roff = self.cpart = self.ccnt = None
         if CELLS and not DETERMINISTIC and values.device.type == "cuda" and self.P and d > 0:
@@ -622,6 +623,7 @@ class BatchCsc:
         assert self.cap == 0
         self.ET = self.EL = self.EB = self.tstride = 0
         self.cells, self.rstride = 0, 1
+        self.S = self.CS = self.cb = 0
 
     @staticmethod
     def build(indptr, indices, values, n: int, d: int, B: int):
@@ -906,7 +908,7 @@ def csc_round(csc: BatchCsc, indptr, idx, val, y, wt, coef, n, d, B, loss, state
                 native.ptr(mult), native.ptr(wl), native.ptr(csc.colptr), native.ptr(csc.erow), native.ptr(csc.evals),
                 native.ptr(fb), int(fuse), max_iter, tol, lr, reg, en, native.ptr(csc.tiles), native.ptr(csc.ntiles),
                 csc.tstride, csc.rb, csc.EL, csc.ET, native.ptr(csc.cent), native.ptr(csc.cval), native.ptr(csc.roff),
-                csc.rstride, csc.rbb, getattr(csc, "S", 0), getattr(csc, "CS", 0), getattr(csc, "cb", 0), csc.cells, csc.cmax,
+                csc.rstride, csc.rbb, csc.S, csc.CS, csc.cb, csc.cells, csc.cmax,
                 native.ptr(csc.cpart), native.ptr(csc.ccnt), native.stream_ptr(val.device))
 
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-block timeline of the tiled sparse backward (glm.hip glm_csc_tile_bwd_kernel) at the SVC
+"""Per-block timeline of the tiled sparse backward (glm_sparse.hip glm_csc_tile_bwd_kernel) at the SVC
 shard shape (6.25M x 1M, 64 nnz/row, batch 100k): s_memrealtime stamps (100 MHz) at block entry,
 after the thread's own gathers, after the block barrier (all gathers of the tile done) and after
 the column pass, summarised per round relative to the earliest block entry.

@@ -1,5 +1,5 @@
 """Host-side rules of the sparse forward's cells (ops/glm.py BatchCsc._pick_cells) and the
-XCD-aware block order of glm.hip glm_csr_cell_fwd_kernel, checked without a GPU: the shape the
+XCD-aware block order of glm_sparse.hip glm_csr_cell_fwd_kernel, checked without a GPU: the shape the
 picker chooses for the SVC north-star shard, denser rows, narrow models, and that the kernel's
 blockIdx → cell map is a bijection of the grid for every grid size."""
 import types
@@ -64,7 +64,7 @@ def test_fp64_cells_respect_lds(monkeypatch):
 
 @pytest.mark.parametrize("grid", list(range(1, 70)) + [490, 491, 497, 588, 784, 1176])
 def test_xcd_block_order_is_a_bijection(grid):
-    # glm.hip glm_csr_cell_fwd_kernel: XCD x = b mod 8 holds ceil((grid - x) / 8) blocks and
+    # glm_sparse.hip glm_csr_cell_fwd_kernel: XCD x = b mod 8 holds ceil((grid - x) / 8) blocks and
     # starts at x·floor(grid/8) + min(x, grid mod 8)
     q, r = grid >> 3, grid & 7
     got = sorted((b & 7) * q + min(b & 7, r) + (b >> 3) for b in range(grid))
