@@ -23,6 +23,7 @@
 // Ties are rows with equal scores (+0 and −0 equal, every NaN its own group), as the reference's
 // `score != t.f0` test; rows of a tie keep their input order (the sort is stable).
 #include "common.h"
+#include "scan.h"
 
 namespace {
 
@@ -80,26 +81,7 @@ __global__ __launch_bounds__(BC_THREADS) void bc_keys_kernel(const double* __res
   }
 }
 
-// --- block scans over one value per thread (BC_THREADS threads) ---------------------------------
-template <typename T, typename Op>
-__device__ __forceinline__ T block_excl_scan(T v, T ident, Op op, T* sh) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  T inc = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const T o = __shfl_up(inc, off, 64);
-    if (lane >= off) inc = op(inc, o);
-  }
-  if (lane == 63) sh[w] = inc;
-  __syncthreads();
-  T pre = ident;
-  for (int q = 0; q < w; ++q) pre = op(pre, sh[q]);
-  T ex = __shfl_up(inc, 1, 64);
-  if (lane == 0) ex = ident;
-  __syncthreads();
-  return op(pre, ex);
-}
-
+// --- the suffix block scan over one value per thread (BC_THREADS threads); forward ones: scan.h --
 template <typename T, typename Op>
 __device__ __forceinline__ T block_excl_suffix_scan(T v, T ident, Op op, T* sh) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -119,14 +101,8 @@ __device__ __forceinline__ T block_excl_suffix_scan(T v, T ident, Op op, T* sh) 
   return op(suf, ex);
 }
 
-struct Lmax {
-  __device__ long operator()(long a, long b) const { return a > b ? a : b; }
-};
 struct Lmin {
   __device__ long operator()(long a, long b) const { return a < b ? a : b; }
-};
-struct Iadd {
-  __device__ int operator()(int a, int b) const { return a + b; }
 };
 
 // the thread's rows of tile t: sorted positions r0 … r0 + cnt − 1
@@ -235,58 +211,28 @@ __global__ __launch_bounds__(BC_THREADS) void bc_agg_kernel(const uint64_t* __re
 // chunks of 1024 tiles with block scans (forward for the first three, backward for the tails)
 __global__ __launch_bounds__(1024) void bc_carry_kernel(const long* __restrict__ agg, long nt,
                                                         long* __restrict__ carry) {
-  __shared__ long wsum[3][16];
-  __shared__ long run[3];
+  __shared__ long wsum[16];
   __shared__ long runmin;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (threadIdx.x == 0) {
-    run[0] = 0;
-    run[1] = 0;
-    run[2] = -1;
-    runmin = 0x7fffffffffffffffL;
-  }
+  if (threadIdx.x == 0) runmin = 0x7fffffffffffffffL;
   __syncthreads();
+  long ra = 0, rb = 0, rh = -1;  // the passes before this one
   for (long base = 0; base < nt; base += 1024) {
     const long t = base + threadIdx.x;
     const bool ok = t < nt;
-    long a = ok ? agg[t * 4 + 0] : 0, b = ok ? agg[t * 4 + 1] : 0, h = ok ? agg[t * 4 + 2] : -1;
-    long ia = a, ib = b, ih = h;  // inclusive wave scans
-    for (int off = 1; off < 64; off <<= 1) {
-      const long oa = __shfl_up(ia, off, 64), ob = __shfl_up(ib, off, 64), oh = __shfl_up(ih, off, 64);
-      if (lane >= off) {
-        ia += oa;
-        ib += ob;
-        ih = oh > ih ? oh : ih;
-      }
-    }
-    if (lane == 63) {
-      wsum[0][w] = ia;
-      wsum[1][w] = ib;
-      wsum[2][w] = ih;
-    }
-    __syncthreads();
-    long pa = run[0], pb = run[1], ph = run[2];
-    for (int q = 0; q < w; ++q) {
-      pa += wsum[0][q];
-      pb += wsum[1][q];
-      ph = wsum[2][q] > ph ? wsum[2][q] : ph;
-    }
-    const long ea = pa + ia - a, eb = pb + ib - b;  // exclusive
-    long eh = __shfl_up(ih, 1, 64);
-    if (lane == 0) eh = -1;
-    eh = eh > ph ? eh : ph;
+    const long a = ok ? agg[t * 4 + 0] : 0, b = ok ? agg[t * 4 + 1] : 0, h = ok ? agg[t * 4 + 2] : -1;
+    long ta, tb, th;
+    const long ea = ra + block_excl_scan<1024>(a, wsum, &ta);
+    const long eb = rb + block_excl_scan<1024>(b, wsum, &tb);
+    const long eh = ScanMax()(rh, block_excl_scan<1024>(h, -1L, ScanMax(), wsum, &th));
     if (ok) {
       carry[t * 4 + 0] = ea;
       carry[t * 4 + 1] = eb;
       carry[t * 4 + 2] = eh;
     }
-    __syncthreads();
-    if (threadIdx.x == 1023) {
-      run[0] = ea + a;
-      run[1] = eb + b;
-      run[2] = (h > eh ? h : eh);
-    }
-    __syncthreads();
+    ra += ta;
+    rb += tb;
+    rh = ScanMax()(rh, th);
   }
   for (long top = nt; top > 0; top -= 1024) {
     const long base = top > 1024 ? top - 1024 : 0;
@@ -298,10 +244,10 @@ __global__ __launch_bounds__(1024) void bc_carry_kernel(const long* __restrict__
       const long o = __shfl_down(iv, off, 64);
       if (lane + off < 64) iv = o < iv ? o : iv;
     }
-    if (lane == 0) wsum[0][w] = iv;
+    if (lane == 0) wsum[w] = iv;
     __syncthreads();
     long sm = runmin;
-    for (int q = 15; q > w; --q) sm = wsum[0][q] < sm ? wsum[0][q] : sm;
+    for (int q = 15; q > w; --q) sm = wsum[q] < sm ? wsum[q] : sm;
     long ev = __shfl_down(iv, 1, 64);
     if (lane == 63) ev = 0x7fffffffffffffffL;
     ev = ev < sm ? ev : sm;
@@ -370,9 +316,9 @@ __global__ __launch_bounds__(BC_THREADS) void bc_metrics_kernel(const uint64_t* 
     }
   }
   // carries into this thread: counts before it, last head before it, first tail after it
-  const int cp_in = block_excl_scan<int>(np, 0, Iadd(), shi);
-  const int cn_in = block_excl_scan<int>(nn, 0, Iadd(), shi);
-  long hin = block_excl_scan<long>(head, -1, Lmax(), shl);
+  const int cp_in = block_excl_scan<BC_THREADS>(np, shi);
+  const int cn_in = block_excl_scan<BC_THREADS>(nn, shi);
+  long hin = block_excl_scan<BC_THREADS>(head, -1L, ScanMax(), shl);
   long tin = block_excl_suffix_scan<long>(tail, 0x7fffffffffffffffL, Lmin(), shl);
   hin = hin > cy[2] ? hin : cy[2];
   tin = tin < cy[3] ? tin : cy[3];

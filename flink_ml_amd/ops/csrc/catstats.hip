@@ -20,6 +20,7 @@
 //              carry) → codes[column][row], the distinct values and their columns;
 //   cs_chist   counts[code][label] of every (row, column) with integer atomics.
 #include "common.h"
+#include "scan.h"
 
 namespace {
 
@@ -336,27 +337,14 @@ __global__ __launch_bounds__(CS_THREADS) void cs_heads_kernel(const uint64_t* __
 
 // one block: tcnt ← exclusive prefix; tcnt[nt] = total distinct
 __global__ __launch_bounds__(1024) void cs_scan_kernel(long* __restrict__ tcnt, long nt) {
-  __shared__ long s[1024];
-  __shared__ long run;
-  if (threadIdx.x == 0) run = 0;
-  __syncthreads();
+  __shared__ long tmp[16];
+  long run = 0;
   for (long base = 0; base < nt; base += 1024) {
     const long t = base + threadIdx.x;
-    s[threadIdx.x] = t < nt ? tcnt[t] : 0;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      long a = run;
-      const long m = nt - base < 1024 ? nt - base : 1024;
-      for (long i = 0; i < m; ++i) {
-        const long v = s[i];
-        s[i] = a;
-        a += v;
-      }
-      run = a;
-    }
-    __syncthreads();
-    if (t < nt) tcnt[t] = s[threadIdx.x];
-    __syncthreads();
+    long tot;
+    const long ex = run + block_excl_scan<1024>(t < nt ? tcnt[t] : 0L, tmp, &tot);
+    if (t < nt) tcnt[t] = ex;
+    run += tot;
   }
   if (threadIdx.x == 0) tcnt[nt] = run;
 }
@@ -380,18 +368,8 @@ __global__ __launch_bounds__(CS_THREADS) void cs_codes_kernel(const uint64_t* __
     hd[q] = e < total && cs_head(keys, e, n);
     hc += hd[q];
   }
-  // block exclusive scan of hc
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  long inc = hc;
-  for (int off = 1; off < 64; off <<= 1) {
-    const long o = __shfl_up(inc, off, 64);
-    if (lane >= off) inc += o;
-  }
-  if (lane == 63) sh[w] = inc;
-  __syncthreads();
-  long pre = 0;
-  for (int q = 0; q < w; ++q) pre += sh[q];
-  long g = gid_base + tcnt[blockIdx.x] + pre + inc - hc - 1;  // gid of the entry before my first
+  const long pre = block_excl_scan<CS_THREADS>((long)hc, sh);  // heads before my entries in the tile
+  long g = gid_base + tcnt[blockIdx.x] + pre - 1;  // gid of the entry before my first
 #pragma unroll
   for (int q = 0; q < CS_PER; ++q) {
     const long e = e0 + q;
@@ -408,7 +386,7 @@ __global__ __launch_bounds__(CS_THREADS) void cs_codes_kernel(const uint64_t* __
   // second sweep (colfirst of my column is written by the block holding the column's first
   // entry, possibly another block): codes are written as global ids here and made column-
   // relative by cs_relcodes_kernel
-  g = gid_base + tcnt[blockIdx.x] + pre + inc - hc - 1;
+  g = gid_base + tcnt[blockIdx.x] + pre - 1;
 #pragma unroll
   for (int q = 0; q < CS_PER; ++q) {
     const long e = e0 + q;

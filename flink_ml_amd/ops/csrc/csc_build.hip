@@ -30,6 +30,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "scan.h"
 
 namespace {
 
@@ -224,28 +225,9 @@ __global__ __launch_bounds__(TL_THREADS) void csc_tiles_scan_kernel(int* __restr
                                                                     const int* __restrict__ colptr, long b0, int d,
                                                                     int2* __restrict__ tiles, int tstride,
                                                                     int* __restrict__ ntiles) {
-  int* __restrict__ cc = cnt + (long)blockIdx.x * nchunks;
-  const int per = (nchunks + TL_THREADS - 1) / TL_THREADS;
-  const int i0 = (int)threadIdx.x * per;
-  int loc = 0;
-  for (int i = i0; i < i0 + per && i < nchunks; ++i) loc += cc[i];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int inc = loc;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int v = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += v;
-  }
   __shared__ int wtot[TL_THREADS / 64];
-  if (lane == 63) wtot[w] = inc;
-  __syncthreads();
-  int off = inc - loc;
-  for (int i = 0; i < w; ++i) off += wtot[i];
-  for (int i = i0; i < i0 + per && i < nchunks; ++i) {  // counts → exclusive offsets, in place
-    const int v = cc[i];
-    cc[i] = off;
-    off += v;
-  }
+  int* cc = cnt + (long)blockIdx.x * nchunks;
+  const int off = block_excl_scan_array<TL_THREADS>(cc, cc, nchunks, wtot);  // counts → offsets, in place
   if (threadIdx.x == TL_THREADS - 1) {
     const long b = b0 + blockIdx.x;
     const int nt = off < tstride - 1 ? off : tstride - 1;  // (bounded by construction)

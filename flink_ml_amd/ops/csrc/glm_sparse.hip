@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "glm_core.h"
+#include "scan.h"
 
 namespace {
 
@@ -684,53 +685,6 @@ struct BktArgs {
   void* acc;       // [d] zero between rounds: partial slices of multi-chunk buckets
 };
 
-// exclusive scan of one int per thread over the block (NT threads); *total = the sum
-template <int NT = BK_NT>
-__device__ __forceinline__ int bk_exscan(int v, int* tmp, int* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(x, o, 64);
-    if (lane >= o) x += t;
-  }
-  if (lane == 63) tmp[w] = x;
-  __syncthreads();
-  if (w == 0) {
-    int s = lane < NT / 64 ? tmp[lane] : 0;
-#pragma unroll
-    for (int o = 1; o < NT / 64; o <<= 1) {
-      const int t = __shfl_up(s, o, 64);
-      if (lane >= o) s += t;
-    }
-    if (lane < NT / 64) tmp[lane] = s;
-  }
-  __syncthreads();
-  const int pre = w ? tmp[w - 1] : 0;
-  *total = tmp[NT / 64 - 1];
-  __syncthreads();  // (tmp is reused by the next scan)
-  return pre + x - v;
-}
-
-// exclusive scan of v[0..m) into out[0..m) (LDS or global) by the whole block, each thread a run
-// of consecutive values; returns the total
-template <int NT = BK_NT>
-__device__ __forceinline__ int bk_exscan_array(const int* v, int* out, int m, int* tmp, long ostride = 1) {
-  const int per = (m + NT - 1) / NT;
-  const int q0 = threadIdx.x * per;
-  int mine = 0;
-  for (int i = 0; i < per; ++i) mine += q0 + i < m ? v[q0 + i] : 0;
-  int total;
-  int run = bk_exscan<NT>(mine, tmp, &total);
-  for (int i = 0; i < per; ++i)
-    if (q0 + i < m) {
-      const int c = v[q0 + i];
-      out[(long)(q0 + i) * ostride] = run;
-      run += c;
-    }
-  return total;
-}
-
 __device__ __forceinline__ bool bk_batch(const int* state, long n, long B, long& start, long& end, int& e) {
   if (!round_running(state, e)) return false;
   batch_rows(round_batch(e, n, B), n, B, start, end);
@@ -840,13 +794,7 @@ __global__ __launch_bounds__(BK_NT) void glm_bkt_count_kernel(const long* __rest
     const int q0 = ln * per;
     int sum = 0;
     for (int i = 0; i < per; ++i) sum += q0 + i < k.nb ? h[q0 + i] : 0;
-    int x = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(x, o, 64);
-      if (ln >= o) x += t;
-    }
-    int run = x - sum;
+    int run = wave_incl_scan(sum) - sum;
     for (int i = 0; i < per; ++i)
       if (q0 + i < k.nb) {
         const int c = h[q0 + i];
@@ -867,7 +815,7 @@ __global__ __launch_bounds__(BK_NT) void glm_bkt_scan_kernel(long n, long B, con
   const int nfb = (int)((end - start + k.rb - 1) / k.rb);
   const int b = blockIdx.x;
   const long row = slot * k.mstride + (long)b * nfb;
-  const int total = bk_exscan_array(k.cntm + row, k.cntm + row, nfb, tmp);
+  const int total = block_excl_scan_array<BK_NT>(k.cntm + row, k.cntm + row, nfb, tmp);
   if (threadIdx.x == 0) k.tot[slot * k.nb + b] = total;
 }
 
@@ -883,7 +831,7 @@ __global__ __launch_bounds__(BK_NT) void glm_bkt_base_kernel(long n, long B, con
   long start, end, slot;
   if (!bk_count_batch(state, n, B, k, start, end, slot)) return;
   const int nfb = (int)((end - start + k.rb - 1) / k.rb);
-  sb[k.nb] = bk_exscan_array(k.tot + slot * k.nb, sb, k.nb, tmp);
+  sb[k.nb] = block_excl_scan_array<BK_NT>(k.tot + slot * k.nb, sb, k.nb, tmp);
   __syncthreads();
   if (blockIdx.x == 0)
     for (int i = threadIdx.x; i <= k.nb; i += BK_NT) k.bst[slot * (k.nb + 1) + i] = sb[i];
@@ -1058,7 +1006,7 @@ __global__ __launch_bounds__(SC_NT) void glm_bkt_fwd_scatter_kernel(
     __syncthreads();
     for (int t = tid; t < pe; t += SC_NT) srow[t] = (uint16_t)atomicAdd(&ph[idx[jb + p0 + t] >> csb], 1);
     __syncthreads();
-    bk_exscan_array<SC_NT>(ph, pofs, k.nb, tmp);
+    block_excl_scan_array<SC_NT>(ph, pofs, k.nb, tmp);
     __syncthreads();
     for (int t = tid; t < pe; t += SC_NT) {
       const int j = p0 + t;
@@ -1123,7 +1071,7 @@ __global__ __launch_bounds__(BK_NT) void glm_bkt_bwd_kernel(const long* __restri
     nch[i] = len > k.chunk ? (len + k.chunk - 1) / k.chunk : 1;
   }
   __syncthreads();
-  iofs[k.nb] = bk_exscan_array(nch, iofs, k.nb, tmp);
+  iofs[k.nb] = block_excl_scan_array<BK_NT>(nch, iofs, k.nb, tmp);
   __syncthreads();
   const int T = iofs[k.nb];
   const int CS = 1 << k.csb;  // ≤ 4 · BK_NT (host-checked csb ≤ 12)
@@ -1171,7 +1119,7 @@ __global__ __launch_bounds__(BK_NT) void glm_bkt_bwd_kernel(const long* __restri
     __syncthreads();
     // column starts (exclusive scan of the counts; cc[c] becomes the column's slot cursor and the
     // counts are recovered from the next column's start after the scatter)
-    cc[CS] = bk_exscan_array(cc, cc, CS, tmp);
+    cc[CS] = block_excl_scan_array<BK_NT>(cc, cc, CS, tmp);
     __syncthreads();
     // pass 2: values into their column's slots
 #pragma unroll

@@ -17,6 +17,7 @@
 // deterministic mode (FMLX_DETERMINISTIC=1) keeps the stable radix sort (sort.hip).
 // Keys outside [0, k) are dropped from the grouping (counted nowhere).
 #include "common.h"
+#include "scan.h"
 
 namespace {
 constexpr int GS_TILE = 8192;
@@ -43,35 +44,15 @@ __global__ __launch_bounds__(GS_THREADS) void group_hist_kernel(const int* __res
 __global__ __launch_bounds__(GS_THREADS) void group_scan_kernel(int* __restrict__ counts, int k, int chunk,
                                                                 long* __restrict__ offsets, long* __restrict__ chunk_off,
                                                                 int* __restrict__ cursor) {
-  __shared__ long wtot[2][GS_THREADS / 64];
-  __shared__ long carry[2];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (threadIdx.x < 2) carry[threadIdx.x] = 0;
-  __syncthreads();
+  __shared__ long wtot[GS_THREADS / 64];
+  long carry0 = 0, carry1 = 0;
   for (int base = 0; base <= k; base += GS_THREADS) {
     const int c = base + threadIdx.x;
     const long cnt = c < k ? counts[c] : 0;
     const long chk = chunk > 0 ? (cnt + chunk - 1) / chunk : 0;
-    long i0 = cnt, i1 = chk;  // inclusive wave scans of both sequences
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const long o0 = __shfl_up(i0, off, 64), o1 = __shfl_up(i1, off, 64);
-      if (lane >= off) {
-        i0 += o0;
-        i1 += o1;
-      }
-    }
-    if (lane == 63) {
-      wtot[0][wv] = i0;
-      wtot[1][wv] = i1;
-    }
-    __syncthreads();
-    long p0 = 0, p1 = 0;
-    for (int i = 0; i < wv; ++i) {
-      p0 += wtot[0][i];
-      p1 += wtot[1][i];
-    }
-    const long e0 = carry[0] + p0 + i0 - cnt, e1 = carry[1] + p1 + i1 - chk;
+    long t0, t1;
+    const long e0 = carry0 + block_excl_scan<GS_THREADS>(cnt, wtot, &t0);
+    const long e1 = carry1 + block_excl_scan<GS_THREADS>(chk, wtot, &t1);
     if (c <= k) {
       offsets[c] = e0;
       if (chunk_off) chunk_off[c] = e1;
@@ -80,12 +61,8 @@ __global__ __launch_bounds__(GS_THREADS) void group_scan_kernel(int* __restrict_
       cursor[c] = (int)e0;
       counts[c] = 0;  // ready for the next round's histogram
     }
-    __syncthreads();
-    if (threadIdx.x == GS_THREADS - 1) {
-      carry[0] = e0 + cnt;
-      carry[1] = e1 + chk;
-    }
-    __syncthreads();
+    carry0 += t0;
+    carry1 += t1;
   }
 }
 
@@ -185,11 +162,8 @@ __global__ __launch_bounds__(256) void st_colscan_kernel(int* __restrict__ T, in
 // one block: S[g][c] ← key offset + exclusive prefix over groups; offsets / chunk offsets
 __global__ __launch_bounds__(1024) void st_base_kernel(int* __restrict__ S, int groups, int k, int chunk,
                                                       long* __restrict__ offsets, long* __restrict__ chunk_off) {
-  __shared__ long wtot[2][16];
-  __shared__ long carry[2];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (threadIdx.x < 2) carry[threadIdx.x] = 0;
-  __syncthreads();
+  __shared__ long wtot[16];
+  long carry0 = 0, carry1 = 0;
   for (int base = 0; base <= k; base += 1024) {
     const int c = base + threadIdx.x;
     long cnt = 0;
@@ -201,38 +175,17 @@ __global__ __launch_bounds__(1024) void st_base_kernel(int* __restrict__ S, int 
       }
     }
     const long chk = chunk > 0 ? (cnt + chunk - 1) / chunk : 0;
-    long i0 = cnt, i1 = chk;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const long o0 = __shfl_up(i0, off, 64), o1 = __shfl_up(i1, off, 64);
-      if (lane >= off) {
-        i0 += o0;
-        i1 += o1;
-      }
-    }
-    if (lane == 63) {
-      wtot[0][wv] = i0;
-      wtot[1][wv] = i1;
-    }
-    __syncthreads();
-    long p0 = 0, p1 = 0;
-    for (int i = 0; i < wv; ++i) {
-      p0 += wtot[0][i];
-      p1 += wtot[1][i];
-    }
-    const long e0 = carry[0] + p0 + i0 - cnt, e1 = carry[1] + p1 + i1 - chk;
+    long t0, t1;
+    const long e0 = carry0 + block_excl_scan<1024>(cnt, wtot, &t0);
+    const long e1 = carry1 + block_excl_scan<1024>(chk, wtot, &t1);
     if (c <= k) {
       offsets[c] = e0;
       if (chunk_off) chunk_off[c] = e1;
     }
     if (c < k)
       for (int g = 0; g < groups; ++g) S[(long)g * k + c] += (int)e0;
-    __syncthreads();
-    if (threadIdx.x == 1023) {
-      carry[0] = e0 + cnt;
-      carry[1] = e1 + chk;
-    }
-    __syncthreads();
+    carry0 += t0;
+    carry1 += t1;
   }
 }
 

@@ -26,6 +26,7 @@
 //  * kmeans_finalize: c = sum·(1/count) (KMeans.java:205), weights = counts, and the padded bf16
 //    copy + ‖c‖² used by the next round's MFMA assign.
 #include "common.h"
+#include "scan.h"
 
 namespace {
 
@@ -850,9 +851,6 @@ __global__ __launch_bounds__(256) void kmeans_chunk_sum_bf16v_kernel(const bf16_
 __global__ __launch_bounds__(1024) void kmeans_offsets_kernel(const int* __restrict__ keys_sorted, long n, int k,
                                                               long* __restrict__ offsets, long* __restrict__ chunk_off) {
   __shared__ long warp_tot[16];
-  __shared__ long carry;
-  if (threadIdx.x == 0) carry = 0;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   // 1. offsets[c] = lower_bound(keys_sorted, c) for c = 0..k, every cluster's search in parallel
   for (int c = threadIdx.x; c <= k; c += 1024) {
     long lo = 0, hi = n;
@@ -863,27 +861,16 @@ __global__ __launch_bounds__(1024) void kmeans_offsets_kernel(const int* __restr
     offsets[c] = lo;
   }
   __syncthreads();  // this block's global writes are visible to the block after the barrier
-  // 2. chunk_off = exclusive scan of ceil(count / KM_CH), fixed order (wave prefix, wave totals,
-  // carry across 1024-cluster passes); counts from neighbouring offsets — one binary search per
-  // cluster instead of two dependent ones
+  // 2. chunk_off = exclusive scan of ceil(count / KM_CH), a carry across 1024-cluster passes;
+  // counts from neighbouring offsets — one binary search per cluster instead of two dependent ones
+  long carry = 0;
   for (int base = 0; base <= k; base += 1024) {
     const int c = base + threadIdx.x;
     const long chunks = c < k ? (offsets[c + 1] - offsets[c] + KM_CH - 1) / KM_CH : 0;
-    long incl = chunks;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const long o = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += o;
-    }
-    if (lane == 63) warp_tot[wv] = incl;
-    __syncthreads();
-    long wpre = 0;
-    for (int i = 0; i < wv; ++i) wpre += warp_tot[i];
-    const long excl = carry + wpre + incl - chunks;
+    long tot;
+    const long excl = carry + block_excl_scan<1024>(chunks, warp_tot, &tot);
     if (c <= k) chunk_off[c] = excl;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = excl + chunks;
-    __syncthreads();
+    carry += tot;
   }
 }
 

@@ -21,6 +21,7 @@
 // The row is re-read once per pass (at most 3 + 2 for fp32 / 6 + 2 for fp64); it stays in L2 /
 // the Infinity Cache for the usual query blocks.
 #include "common.h"
+#include "scan.h"
 
 #include <math.h>
 #include <stdint.h>
@@ -44,33 +45,6 @@ struct SelKey<double> {
   typedef unsigned long long U;
   __device__ static U bits(double v) { return (U)__double_as_longlong(fabs(v)); }
 };
-
-// exclusive scan of one int per thread over the block; *total = the sum
-__device__ __forceinline__ int sel_exscan(int v, int* tmp, int* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(x, o, 64);
-    if (lane >= o) x += t;
-  }
-  if (lane == 63) tmp[w] = x;
-  __syncthreads();
-  if (w == 0) {
-    int s = lane < SEL_NT / 64 ? tmp[lane] : 0;
-#pragma unroll
-    for (int o = 1; o < SEL_NT / 64; o <<= 1) {
-      const int t = __shfl_up(s, o, 64);
-      if (lane >= o) s += t;
-    }
-    if (lane < SEL_NT / 64) tmp[lane] = s;
-  }
-  __syncthreads();
-  const int pre = w ? tmp[w - 1] : 0;
-  *total = tmp[SEL_NT / 64 - 1];
-  __syncthreads();
-  return pre + x - v;
-}
 
 template <typename A>
 __global__ __launch_bounds__(SEL_NT) void knn_select_kernel(const A* __restrict__ G, long ldg, long n,
@@ -131,7 +105,7 @@ __global__ __launch_bounds__(SEL_NT) void knn_select_kernel(const A* __restrict_
     // the bin holding the rem-th smallest of the keys still in play (two bins per thread)
     const int h0 = hist[2 * tid], h1 = hist[2 * tid + 1];
     int tot;
-    const int before = sel_exscan(h0 + h1, tmp, &tot);
+    const int before = block_excl_scan<SEL_NT>(h0 + h1, tmp, &tot);
     if (before < rem && rem <= before + h0) {
       s_digit = 2 * tid;
       s_rem = rem - before;

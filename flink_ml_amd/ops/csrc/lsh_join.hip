@@ -27,6 +27,7 @@
 //
 // Integer work only apart from that division; ordinary vector stores and global integer atomics.
 #include "common.h"
+#include "scan.h"
 
 namespace {
 
@@ -168,27 +169,13 @@ __global__ __launch_bounds__(LJ_THREADS) void scan_reduce_kernel(const int* __re
 __global__ __launch_bounds__(1024) void scan_sums_kernel(long* __restrict__ bsum, long nb, long* __restrict__ off_end,
                                                          long* __restrict__ total) {
   __shared__ long wtot[16];
-  __shared__ long carry;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
+  long carry = 0;
   for (long b0 = 0; b0 < nb; b0 += 1024) {
     const long b = b0 + threadIdx.x;
-    const long v = b < nb ? bsum[b] : 0;
-    long inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const long o = __shfl_up(inc, off, 64);
-      if (lane >= off) inc += o;
-    }
-    if (lane == 63) wtot[wv] = inc;
-    __syncthreads();
-    long p = carry;
-    for (int i = 0; i < wv; ++i) p += wtot[i];
-    if (b < nb) bsum[b] = p + inc - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = p + inc;
-    __syncthreads();
+    long tot;
+    const long ex = carry + block_excl_scan<1024>(b < nb ? bsum[b] : 0L, wtot, &tot);
+    if (b < nb) bsum[b] = ex;
+    carry += tot;
   }
   if (threadIdx.x == 0) {
     *off_end = carry;
@@ -201,7 +188,6 @@ __global__ __launch_bounds__(LJ_THREADS) void scan_apply_kernel(const int* __res
                                                                 const long* __restrict__ bsum,
                                                                 long* __restrict__ off) {
   __shared__ long wtot[LJ_THREADS / 64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const long i0 = (long)blockIdx.x * SC_TILE + (long)threadIdx.x * SC_PER_THREAD;
   int c[SC_PER_THREAD];
   long v = 0;
@@ -210,16 +196,7 @@ __global__ __launch_bounds__(LJ_THREADS) void scan_apply_kernel(const int* __res
     c[j] = i0 + j < n ? cnt[i0 + j] : 0;
     v += c[j];
   }
-  long inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const long x = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += x;
-  }
-  if (lane == 63) wtot[wv] = inc;
-  __syncthreads();
-  long p = bsum[blockIdx.x] + inc - v;
-  for (int i = 0; i < wv; ++i) p += wtot[i];
+  long p = bsum[blockIdx.x] + block_excl_scan<LJ_THREADS>(v, wtot);
 #pragma unroll
   for (int j = 0; j < SC_PER_THREAD; ++j) {
     if (i0 + j < n) off[i0 + j] = p;

@@ -25,6 +25,7 @@
 //               run by digit run.
 // Every step is order-deterministic; no global atomics.
 #include "common.h"
+#include "scan.h"
 
 namespace {
 
@@ -143,12 +144,9 @@ __global__ __launch_bounds__(256) void rs_colscan_kernel(int* __restrict__ T, Se
 // one block per segment: G[g][c] ← segment start + digit prefix + group prefix
 __global__ __launch_bounds__(1024) void rs_base_kernel(int* __restrict__ G, SegTable tb, int nd) {
   __shared__ long wtot[16];
-  __shared__ long carry;
   const int s = blockIdx.x;
   const int g0 = tb.grp0[s], g1 = tb.grp0[s + 1];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry = tb.bound[s];
-  __syncthreads();
+  long carry = tb.bound[s];
   for (int base = 0; base < nd; base += 1024) {
     const int c = base + threadIdx.x;
     long cnt = 0;
@@ -158,22 +156,11 @@ __global__ __launch_bounds__(1024) void rs_base_kernel(int* __restrict__ G, SegT
         G[(long)g * nd + c] = (int)cnt;
         cnt += v;
       }
-    long inc = cnt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const long o = __shfl_up(inc, off, 64);
-      if (lane >= off) inc += o;
-    }
-    if (lane == 63) wtot[wv] = inc;
-    __syncthreads();
-    long p = 0;
-    for (int i = 0; i < wv; ++i) p += wtot[i];
-    const long ex = carry + p + inc - cnt;  // first position of digit c in the segment
+    long tot;
+    const long ex = carry + block_excl_scan<1024>(cnt, wtot, &tot);  // first position of digit c in the segment
     if (c < nd)
       for (int g = g0; g < g1; ++g) G[(long)g * nd + c] += (int)ex;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = ex + cnt;
-    __syncthreads();
+    carry += tot;
   }
 }
 
@@ -181,7 +168,6 @@ __global__ __launch_bounds__(1024) void rs_base_kernel(int* __restrict__ G, SegT
 // exclusive scan over the digits, block-wide) and hw[q][c] = wave q's cursor for digit c (loc[c]
 // plus the counts of the waves before q). Block-wide; ends with a barrier.
 __device__ __forceinline__ void rs_tile_cursors(int* hw, int nd, int* loc, int* wsum) {
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   constexpr int DPT = 4;  // digits per thread (nd <= RS_THREADS·DPT = 2048)
   int tot[DPT];
   int run = 0;
@@ -195,12 +181,11 @@ __device__ __forceinline__ void rs_tile_cursors(int* hw, int nd, int* loc, int* 
     tot[j] = v;
     run += v;
   }
-  int inc = run;  // inclusive scan of the per-thread sums over the block
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_up(inc, off, 64);
-    if (lane >= off) inc += o;
-  }
+  // the per-thread sums before mine. Not block_excl_scan: the cursor step of a narrow digit (a few
+  // dozen threads with digits at all) is the latency of its barriers, and the barrier that ends
+  // this function already lets wsum be reused (profiles/r14/INDEX.md)
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int inc = wave_incl_scan(run);
   if (lane == 63) wsum[w] = inc;
   __syncthreads();
   int base = inc - run;

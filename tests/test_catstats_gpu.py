@@ -49,6 +49,28 @@ def test_sorted_unique_and_counts():
     assert catstats.flags(torch.tensor([[-4.0, 7.0]]).cuda()) == (-4.0, 7.0, False)
 
 
+def test_distinct_codes_beyond_one_scan_pass():
+    """4 columns × 1,048,577 rows: 1025 tiles of 4096 entries, so the one-block scan of the tiles'
+    distinct counts (cs_scan_kernel) takes a second pass; codes, distinct values and the columns'
+    ranges of them against torch.unique per column."""
+    _need_gpu()
+    from flink_ml_amd.ops import catstats
+
+    g = torch.Generator().manual_seed(9)
+    n, d = 1_048_577, 4
+    assert n * d > 1024 * int(catstats.native.kernels().fmlx_cs_tile()) and d <= catstats.SORT_SEGMENTS
+    X = torch.randint(-5, 23, (n, d), generator=g).double()
+    X[:, 2] = torch.randint(0, 3, (n,), generator=g).double() * 0.5
+    codes, vals = catstats.distinct_codes(X.cuda())
+    assert len(vals) == d
+    # the columns' offsets into the distinct values: every column's range has its own count
+    assert [v.numel() for v in vals] == [torch.unique(X[:, j]).numel() for j in range(d)]
+    for j in range(d):
+        u, inv = torch.unique(X[:, j], sorted=True, return_inverse=True)
+        assert torch.equal(vals[j].cpu(), u)
+        assert torch.equal(codes[j].cpu(), inv.to(torch.int32))
+
+
 @pytest.mark.parametrize("kind", ["int", "int_wide", "float", "float_many"])
 def test_value_label_counts_match_numpy(kind):
     _need_gpu()

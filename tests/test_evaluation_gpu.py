@@ -35,7 +35,8 @@ def test_goldens_on_device():
 @pytest.mark.parametrize("n,kind,weighted", [
     (1, "rand", False), (7, "rand", True), (4096, "ties", False), (4097, "rand", False),
     (50_000, "ties", True), (123_457, "rand", True), (200_000, "nan", False), (60_000, "zeros", False),
-    (30_000, "const", True), (300_000, "ties_wide", False)])
+    (30_000, "const", True), (300_000, "ties_wide", False),
+    (4096 * 1024 + 5, "ties", False)])  # 1025 tiles: the tile carries' one-block scan takes a second pass
 def test_device_metrics_match_torch(n, kind, weighted):
     _need_gpu()
     g = torch.Generator().manual_seed(n)

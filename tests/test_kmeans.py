@@ -339,7 +339,35 @@ def test_gpu_round_offsets_with_empty_clusters():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n,k", [(1, 1), (1000, 7), (3_000_001, 1024), (200_000, 16384)])
+@pytest.mark.parametrize("k", [1023, 1024, 1025, 2500])
+def test_gpu_offsets_kernel_pass_edges(k):
+    """fmlx_kmeans_offsets around its 1024-cluster passes: ~5,000 sorted keys, empty clusters at
+    both ends and in between, one cluster of several chunks; offsets against torch.searchsorted,
+    chunk_off against the cumulative ceil(count / CHUNK)."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from flink_ml_amd.ops import kmeans as kk
+    from flink_ml_amd.ops import native
+
+    g = torch.Generator().manual_seed(k)
+    keys = torch.randint(k // 8, k - k // 8, (4000,), generator=g, dtype=torch.int32) // 2 * 2
+    keys = torch.sort(torch.cat([keys, torch.full((1000,), k // 2, dtype=torch.int32)])).values
+    n = keys.numel()
+    offsets = torch.empty(k + 1, dtype=torch.int64, device="cuda")
+    chunk_off = torch.empty(k + 1, dtype=torch.int64, device="cuda")
+    kd = keys.cuda()
+    native.call("fmlx_kmeans_offsets", native.ptr(kd), n, k, native.ptr(offsets), native.ptr(chunk_off),
+                native.stream_ptr(kd.device))
+    want = torch.searchsorted(keys.long(), torch.arange(k + 1))
+    assert int(want[k // 8 - 1]) == 0 and int(want[k - k // 8]) == n  # empty clusters at both ends
+    assert torch.equal(offsets.cpu(), want)
+    ch = torch.zeros(k + 1, dtype=torch.int64)
+    ch[1:] = torch.cumsum((want[1:] - want[:-1] + kk.CHUNK - 1) // kk.CHUNK, 0)
+    assert torch.equal(chunk_off.cpu(), ch)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,k", [(1, 1), (1000, 7), (5000, 1025), (5000, 3000), (3_000_001, 1024), (200_000, 16384)])
 def test_group_by_key_counting_sort(n, k):
     """The KMeans grouping kernel (csrc/groupsort.hip) against torch: every row once, grouped by
     key, offsets = cumulative counts, chunk offsets = cumulative ceil(count / 256); empty keys,

@@ -364,3 +364,22 @@ def test_keyed_join_two_ranks_native_distances(monkeypatch):
     res = run_spmd(_spmd_keyed_join, 2, env={"FMLX_DEVICE": "cuda:0", "FMLX_XGMI": "0"}, timeout=300)
     assert sorted(r for rows, _ in res for r in rows) == want
     assert [c for _, c in res] == [0, 0]  # no rank computed its distances with the torch formulation
+
+
+@pytest.mark.parametrize("n,cmax", [(0, 4), (1, 4), (2047, 4), (2048, 4), (2049, 4), (1024 * 2048 + 1, 4),
+                                    (20_000, 1 << 20)])
+def test_scan_tile_and_pass_edges(n, cmax):
+    """fmlx_lsh_scan (int32 counts → int64 exclusive offsets) against torch.cumsum in int64: the
+    2048-count tile edge, one tile past a full 1024-tile pass of the one-block scan of the tile
+    sums, and counts up to 2^20 whose total exceeds 2^32; off[n] and the state word's total too."""
+    _need_gpu()
+    g = torch.Generator().manual_seed(n + cmax)
+    cnt = torch.randint(0, cmax + 1, (n,), generator=g, dtype=torch.int32)
+    want = torch.zeros(n + 1, dtype=torch.int64)
+    want[1:] = torch.cumsum(cnt.long(), 0)
+    if cmax > 4:
+        assert int(want[n]) > 1 << 32
+    st = torch.zeros(lsh_ops._ST_WORDS, dtype=torch.int64, device="cuda")
+    off = lsh_ops._scan(cnt.cuda(), st)
+    assert torch.equal(off.cpu(), want)
+    assert int(st[lsh_ops._ST_TOTAL].item()) == int(want[n])
