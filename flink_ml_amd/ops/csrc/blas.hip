@@ -307,61 +307,11 @@ int blocks_for(long work, int per, int cap = 1 << 16) {
   return (int)b;
 }
 
-template <typename T>
-int launch_rowreduce(int tpr, const void* X, long ldx, const void* Y, long ldy, const void* v, long n, int d, int op,
-                     double p, void* out, hipStream_t s) {
-  typedef typename AccOf<T>::type A;
-  const int rows_per_block = 256 / tpr;
-  const int g = blocks_for(n, rows_per_block);
-#define RR(TPR_)                                                                                              \
-  hipLaunchKernelGGL((rowreduce_kernel<T, TPR_>), dim3(g), dim3(256), 0, s, (const T*)X, ldx, (const T*)Y, ldy, \
-                     (const T*)v, n, d, op, p, (A*)out)
-  switch (tpr) {
-    case 4: RR(4); break;
-    case 8: RR(8); break;
-    case 16: RR(16); break;
-    case 32: RR(32); break;
-    default: RR(64); break;
-  }
-#undef RR
-  return (int)hipGetLastError();
-}
-
-template <typename T, typename O>
-int launch_normalize(int tpr, const void* X, long ldx, long n, int d, double p, int pinf, void* out, long ldo,
-                     hipStream_t s) {
-  const int g = blocks_for(n, 256 / tpr);
-#define NK(TPR_)                                                                                                \
-  hipLaunchKernelGGL((normalize_kernel<T, O, TPR_>), dim3(g), dim3(256), 0, s, (const T*)X, ldx, n, d, p, pinf, \
-                     (O*)out, ldo)
-  switch (tpr) {
-    case 4: NK(4); break;
-    case 8: NK(8); break;
-    case 16: NK(16); break;
-    case 32: NK(32); break;
-    default: NK(64); break;
-  }
-#undef NK
-  return (int)hipGetLastError();
-}
-
-template <typename V>
-int launch_csr_rowreduce(int tpr, const long* indptr, const int* idx, const void* val, const double* v, long n, int op,
-                         double p, void* out, hipStream_t s) {
-  typedef typename AccOf<V>::type A;
-  const int g = blocks_for(n, 256 / tpr);
-#define CR(TPR_)                                                                                                   \
-  hipLaunchKernelGGL((csr_rowreduce_kernel<V, TPR_>), dim3(g), dim3(256), 0, s, indptr, idx, (const V*)val, v, n, op, \
-                     p, (A*)out)
-  switch (tpr) {
-    case 4: CR(4); break;
-    case 8: CR(8); break;
-    case 16: CR(16); break;
-    case 32: CR(32); break;
-    default: CR(64); break;
-  }
-#undef CR
-  return (int)hipGetLastError();
+// lanes per row as a compile-time constant: 4 / 8 / 16 / 32, anything else is a whole wave
+template <typename F>
+int with_tpr(int tpr, F&& f) {
+  const bool narrow = tpr == 4 || tpr == 8 || tpr == 16 || tpr == 32;
+  return with_value<4, 8, 16, 32, 64>(narrow ? tpr : 64, f);
 }
 
 }  // namespace
@@ -371,10 +321,16 @@ FMLX_API int fmlx_blas_rowreduce(int dtype, int tpr, const void* X, long ldx, co
                                  long n, int d, int op, double p, void* out, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (n <= 0) return 0;
-  if (dtype == DT_F32) return launch_rowreduce<float>(tpr, X, ldx, Y, ldy, v, n, d, op, p, out, s);
-  if (dtype == DT_F64) return launch_rowreduce<double>(tpr, X, ldx, Y, ldy, v, n, d, op, p, out, s);
-  if (dtype == DT_BF16) return launch_rowreduce<bf16_t>(tpr, X, ldx, Y, ldy, v, n, d, op, p, out, s);
-  return -1;
+  return with_dtype<float, double, bf16_t>(dtype, [&](auto t) {
+    typedef typename decltype(t)::T T;
+    typedef typename decltype(t)::A A;
+    const int g = blocks_for(n, 256 / tpr);
+    return with_tpr(tpr, [&](auto w) {
+      hipLaunchKernelGGL((rowreduce_kernel<T, w.value>), dim3(g), dim3(256), 0, s, (const T*)X, ldx, (const T*)Y, ldy,
+                         (const T*)v, n, d, op, p, (A*)out);
+      return (int)hipGetLastError();
+    });
+  });
 }
 
 // out dtype = the accumulator dtype of X (fp32 for bf16 / fp32, fp64 for fp64)
@@ -382,10 +338,16 @@ FMLX_API int fmlx_blas_normalize(int dtype, int tpr, const void* X, long ldx, lo
                                  void* out, long ldo, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (n <= 0) return 0;
-  if (dtype == DT_F32) return launch_normalize<float, float>(tpr, X, ldx, n, d, p, pinf, out, ldo, s);
-  if (dtype == DT_F64) return launch_normalize<double, double>(tpr, X, ldx, n, d, p, pinf, out, ldo, s);
-  if (dtype == DT_BF16) return launch_normalize<bf16_t, float>(tpr, X, ldx, n, d, p, pinf, out, ldo, s);
-  return -1;
+  return with_dtype<float, double, bf16_t>(dtype, [&](auto t) {
+    typedef typename decltype(t)::T T;
+    typedef typename decltype(t)::A O;
+    const int g = blocks_for(n, 256 / tpr);
+    return with_tpr(tpr, [&](auto w) {
+      hipLaunchKernelGGL((normalize_kernel<T, O, w.value>), dim3(g), dim3(256), 0, s, (const T*)X, ldx, n, d, p, pinf,
+                         (O*)out, ldo);
+      return (int)hipGetLastError();
+    });
+  });
 }
 
 FMLX_API int fmlx_blas_axpby(int dtype, const void* X, long ldx, void* Y, long ldy, long n, int d, double alpha,
@@ -393,18 +355,13 @@ FMLX_API int fmlx_blas_axpby(int dtype, const void* X, long ldx, void* Y, long l
   hipStream_t s = (hipStream_t)stream;
   if (n <= 0 || d <= 0) return 0;
   const int g = blocks_for(n * (long)d, 256, 8192);
-  if (dtype == DT_F32)
-    hipLaunchKernelGGL((axpby_kernel<float, float>), dim3(g), dim3(256), 0, s, (const float*)X, ldx, (float*)Y, ldy, n, d,
-                       (float)alpha, (const float*)alpha_r, (float)beta, (const float*)beta_r);
-  else if (dtype == DT_F64)
-    hipLaunchKernelGGL((axpby_kernel<double, double>), dim3(g), dim3(256), 0, s, (const double*)X, ldx, (double*)Y, ldy,
-                       n, d, alpha, (const double*)alpha_r, beta, (const double*)beta_r);
-  else if (dtype == DT_BF16)
-    hipLaunchKernelGGL((axpby_kernel<bf16_t, float>), dim3(g), dim3(256), 0, s, (const bf16_t*)X, ldx, (bf16_t*)Y, ldy, n,
-                       d, (float)alpha, (const float*)alpha_r, (float)beta, (const float*)beta_r);
-  else
-    return -1;
-  return (int)hipGetLastError();
+  return with_dtype<float, double, bf16_t>(dtype, [&](auto t) {
+    typedef typename decltype(t)::T T;
+    typedef typename decltype(t)::A A;
+    hipLaunchKernelGGL((axpby_kernel<T, A>), dim3(g), dim3(256), 0, s, (const T*)X, ldx, (T*)Y, ldy, n, d, (A)alpha,
+                       (const A*)alpha_r, (A)beta, (const A*)beta_r);
+    return (int)hipGetLastError();
+  });
 }
 
 // out dtype = accumulator dtype of X
@@ -413,18 +370,12 @@ FMLX_API int fmlx_blas_hdot(int dtype, const void* X, long ldx, const double* v,
   hipStream_t s = (hipStream_t)stream;
   if (n <= 0 || d <= 0) return 0;
   const int g = blocks_for(n * (long)d, 256, 8192);
-  if (dtype == DT_F32)
-    hipLaunchKernelGGL((hdot_kernel<float, float>), dim3(g), dim3(256), 0, s, (const float*)X, ldx, v, n, d, (float*)out,
-                       ldo);
-  else if (dtype == DT_F64)
-    hipLaunchKernelGGL((hdot_kernel<double, double>), dim3(g), dim3(256), 0, s, (const double*)X, ldx, v, n, d,
-                       (double*)out, ldo);
-  else if (dtype == DT_BF16)
-    hipLaunchKernelGGL((hdot_kernel<bf16_t, float>), dim3(g), dim3(256), 0, s, (const bf16_t*)X, ldx, v, n, d,
-                       (float*)out, ldo);
-  else
-    return -1;
-  return (int)hipGetLastError();
+  return with_dtype<float, double, bf16_t>(dtype, [&](auto t) {
+    typedef typename decltype(t)::T T;
+    typedef typename decltype(t)::A O;
+    hipLaunchKernelGGL((hdot_kernel<T, O>), dim3(g), dim3(256), 0, s, (const T*)X, ldx, v, n, d, (O*)out, ldo);
+    return (int)hipGetLastError();
+  });
 }
 
 // y = Xᵀ·m (+ beta·y), fp64 y and m; part: scratch [nb · d] of the accumulator dtype.
@@ -436,21 +387,13 @@ FMLX_API int fmlx_blas_gemv_t(int dtype, const void* X, long ldx, const double* 
   const long rpb = n <= 0 ? 0 : (n + nb - 1) / nb;
   const dim3 g1((unsigned)blocks_for(d, 256, 64), (unsigned)nb);
   const int g2 = blocks_for(d, 256);
-  if (dtype == DT_F32) {
-    hipLaunchKernelGGL(gemv_t_part_kernel<float>, g1, dim3(256), 0, s, (const float*)X, ldx, m, n, d, rpb, (float*)part);
-    hipLaunchKernelGGL(gemv_t_sum_kernel<float>, dim3(g2), dim3(256), 0, s, (const float*)part, (int)nb, d, y, beta);
-  } else if (dtype == DT_F64) {
-    hipLaunchKernelGGL(gemv_t_part_kernel<double>, g1, dim3(256), 0, s, (const double*)X, ldx, m, n, d, rpb,
-                       (double*)part);
-    hipLaunchKernelGGL(gemv_t_sum_kernel<double>, dim3(g2), dim3(256), 0, s, (const double*)part, (int)nb, d, y, beta);
-  } else if (dtype == DT_BF16) {
-    hipLaunchKernelGGL(gemv_t_part_kernel<bf16_t>, g1, dim3(256), 0, s, (const bf16_t*)X, ldx, m, n, d, rpb,
-                       (float*)part);
-    hipLaunchKernelGGL(gemv_t_sum_kernel<float>, dim3(g2), dim3(256), 0, s, (const float*)part, (int)nb, d, y, beta);
-  } else {
-    return -1;
-  }
-  return (int)hipGetLastError();
+  return with_dtype<float, double, bf16_t>(dtype, [&](auto t) {
+    typedef typename decltype(t)::T T;
+    typedef typename decltype(t)::A A;
+    hipLaunchKernelGGL(gemv_t_part_kernel<T>, g1, dim3(256), 0, s, (const T*)X, ldx, m, n, d, rpb, (A*)part);
+    hipLaunchKernelGGL(gemv_t_sum_kernel<A>, dim3(g2), dim3(256), 0, s, (const A*)part, (int)nb, d, y, beta);
+    return (int)hipGetLastError();
+  });
 }
 
 // CSR values dtype: DT_F32 / DT_F64
@@ -458,9 +401,16 @@ FMLX_API int fmlx_blas_csr_rowreduce(int vdtype, int tpr, const long* indptr, co
                                      const double* v, long n, int op, double p, void* out, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (n <= 0) return 0;
-  if (vdtype == DT_F32) return launch_csr_rowreduce<float>(tpr, indptr, idx, val, v, n, op, p, out, s);
-  if (vdtype == DT_F64) return launch_csr_rowreduce<double>(tpr, indptr, idx, val, v, n, op, p, out, s);
-  return -1;
+  return with_dtype<float, double>(vdtype, [&](auto t) {
+    typedef typename decltype(t)::T V;
+    typedef typename decltype(t)::A A;
+    const int g = blocks_for(n, 256 / tpr);
+    return with_tpr(tpr, [&](auto w) {
+      hipLaunchKernelGGL((csr_rowreduce_kernel<V, w.value>), dim3(g), dim3(256), 0, s, indptr, idx, (const V*)val, v, n,
+                         op, p, (A*)out);
+      return (int)hipGetLastError();
+    });
+  });
 }
 
 FMLX_API int fmlx_blas_csr_scale(int vdtype, const long* indptr, const int* idx, const void* val, const double* srow,
@@ -468,15 +418,12 @@ FMLX_API int fmlx_blas_csr_scale(int vdtype, const long* indptr, const int* idx,
   hipStream_t s = (hipStream_t)stream;
   if (n <= 0) return 0;
   const int g = blocks_for(n, 256, 16384);
-  if (vdtype == DT_F32)
-    hipLaunchKernelGGL(csr_scale_kernel<float>, dim3(g), dim3(256), 0, s, indptr, idx, (const float*)val, srow, vcol, n,
-                       (float*)out);
-  else if (vdtype == DT_F64)
-    hipLaunchKernelGGL(csr_scale_kernel<double>, dim3(g), dim3(256), 0, s, indptr, idx, (const double*)val, srow, vcol,
-                       n, (double*)out);
-  else
-    return -1;
-  return (int)hipGetLastError();
+  return with_dtype<float, double>(vdtype, [&](auto t) {
+    typedef typename decltype(t)::T V;
+    hipLaunchKernelGGL(csr_scale_kernel<V>, dim3(g), dim3(256), 0, s, indptr, idx, (const V*)val, srow, vcol, n,
+                       (V*)out);
+    return (int)hipGetLastError();
+  });
 }
 
 // Y (fp64 [n, ldy]) += a · CSR (first k columns)
@@ -485,15 +432,12 @@ FMLX_API int fmlx_blas_csr_axpy_dense(int vdtype, const long* indptr, const int*
   hipStream_t s = (hipStream_t)stream;
   if (n <= 0) return 0;
   const int g = blocks_for(n, 256, 16384);
-  if (vdtype == DT_F32)
-    hipLaunchKernelGGL((csr_axpy_dense_kernel<float, double>), dim3(g), dim3(256), 0, s, indptr, idx, (const float*)val,
-                       a, n, k, Y, ldy);
-  else if (vdtype == DT_F64)
-    hipLaunchKernelGGL((csr_axpy_dense_kernel<double, double>), dim3(g), dim3(256), 0, s, indptr, idx,
-                       (const double*)val, a, n, k, Y, ldy);
-  else
-    return -1;
-  return (int)hipGetLastError();
+  return with_dtype<float, double>(vdtype, [&](auto t) {
+    typedef typename decltype(t)::T V;
+    hipLaunchKernelGGL((csr_axpy_dense_kernel<V, double>), dim3(g), dim3(256), 0, s, indptr, idx, (const V*)val, a, n,
+                       k, Y, ldy);
+    return (int)hipGetLastError();
+  });
 }
 
 FMLX_API int fmlx_blas_csr_csr_dot(int vdtype, const long* ap, const int* ai, const void* av, const long* bp,
@@ -501,34 +445,25 @@ FMLX_API int fmlx_blas_csr_csr_dot(int vdtype, const long* ap, const int* ai, co
   hipStream_t s = (hipStream_t)stream;
   if (n <= 0) return 0;
   const int g = blocks_for(n, 256, 16384);
-  if (vdtype == DT_F32)
-    hipLaunchKernelGGL(csr_csr_dot_kernel<float>, dim3(g), dim3(256), 0, s, ap, ai, (const float*)av, bp, bi,
-                       (const float*)bv, n, (float*)out);
-  else if (vdtype == DT_F64)
-    hipLaunchKernelGGL(csr_csr_dot_kernel<double>, dim3(g), dim3(256), 0, s, ap, ai, (const double*)av, bp, bi,
-                       (const double*)bv, n, (double*)out);
-  else
-    return -1;
-  return (int)hipGetLastError();
+  return with_dtype<float, double>(vdtype, [&](auto t) {
+    typedef typename decltype(t)::T V;
+    hipLaunchKernelGGL(csr_csr_dot_kernel<V>, dim3(g), dim3(256), 0, s, ap, ai, (const V*)av, bp, bi, (const V*)bv, n,
+                       (V*)out);
+    return (int)hipGetLastError();
+  });
 }
 
+// esize: bytes per element (the kernel only moves them)
 FMLX_API int fmlx_blas_gather_cols(int esize, const void* X, long ldx, const int* cols, long n, int m, void* out,
                                    void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (n <= 0 || m <= 0) return 0;
   const int g = blocks_for(n * (long)m, 256, 8192);
-  if (esize == 8)
-    hipLaunchKernelGGL(gather_cols_kernel<double>, dim3(g), dim3(256), 0, s, (const double*)X, ldx, cols, n, m,
-                       (double*)out);
-  else if (esize == 4)
-    hipLaunchKernelGGL(gather_cols_kernel<float>, dim3(g), dim3(256), 0, s, (const float*)X, ldx, cols, n, m,
-                       (float*)out);
-  else if (esize == 2)
-    hipLaunchKernelGGL(gather_cols_kernel<bf16_t>, dim3(g), dim3(256), 0, s, (const bf16_t*)X, ldx, cols, n, m,
-                       (bf16_t*)out);
-  else
-    return -1;
-  return (int)hipGetLastError();
+  return with_value<8, 4, 2>(esize, [&](auto e) {
+    typedef std::conditional_t<e.value == 8, double, std::conditional_t<e.value == 4, float, bf16_t>> T;
+    hipLaunchKernelGGL(gather_cols_kernel<T>, dim3(g), dim3(256), 0, s, (const T*)X, ldx, cols, n, m, (T*)out);
+    return (int)hipGetLastError();
+  });
 }
 
 // out [n, m] = products of the columns listed per output term (see gather_prod_kernel); fp32/fp64
@@ -538,15 +473,11 @@ FMLX_API int fmlx_blas_gather_prod(int dtype, const void* X, long ldx, int d, co
   if (n <= 0 || m <= 0) return 0;
   if (deg < 1 || d < 1) return -1;
   const int g = blocks_for(n * (long)m, 256, 8192);
-  if (dtype == DT_F64)
-    hipLaunchKernelGGL(gather_prod_kernel<double>, dim3(g), dim3(256), 0, s, (const double*)X, ldx, d, terms, deg, n,
-                       m, (double*)out);
-  else if (dtype == DT_F32)
-    hipLaunchKernelGGL(gather_prod_kernel<float>, dim3(g), dim3(256), 0, s, (const float*)X, ldx, d, terms, deg, n,
-                       m, (float*)out);
-  else
-    return -1;
-  return (int)hipGetLastError();
+  return with_dtype<double, float>(dtype, [&](auto t) {
+    typedef typename decltype(t)::T T;
+    hipLaunchKernelGGL(gather_prod_kernel<T>, dim3(g), dim3(256), 0, s, (const T*)X, ldx, d, terms, deg, n, m, (T*)out);
+    return (int)hipGetLastError();
+  });
 }
 
 // inputs: k fp64 matrices [n, dim_q] (row stride ld_q); out [n, Π dim_q] fp64

@@ -434,14 +434,12 @@ FMLX_API int fmlx_cs_lds_ints() { return CS_LDS_INTS; }
 FMLX_API int fmlx_cs_flags(int dtype, const void* X, long ld, long n, int d, double* part, double* out, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const unsigned nb = grid_for(n * (long)d, CS_THREADS * 16L, 1024);
-  if (dtype == DT_F64)
-    hipLaunchKernelGGL(cs_flags_kernel<double>, dim3(nb), dim3(CS_THREADS), 0, s, (const double*)X, ld, n, d, part);
-  else if (dtype == DT_F32)
-    hipLaunchKernelGGL(cs_flags_kernel<float>, dim3(nb), dim3(CS_THREADS), 0, s, (const float*)X, ld, n, d, part);
-  else
-    return -1;
-  hipLaunchKernelGGL(cs_flags_final, dim3(1), dim3(64), 0, s, part, (int)nb, out);
-  return (int)hipGetLastError();
+  return with_dtype<double, float>(dtype, [&](auto t) {
+    typedef typename decltype(t)::T T;
+    hipLaunchKernelGGL(cs_flags_kernel<T>, dim3(nb), dim3(CS_THREADS), 0, s, (const T*)X, ld, n, d, part);
+    hipLaunchKernelGGL(cs_flags_final, dim3(1), dim3(64), 0, s, part, (int)nb, out);
+    return (int)hipGetLastError();
+  });
 }
 
 // counts[R] (zeroed by the caller) of the integer values of X[:, col] in [lo, lo + R)
@@ -451,18 +449,11 @@ FMLX_API int fmlx_cs_ihist(int dtype, const void* X, long ld, long n, int col, l
   hipStream_t s = (hipStream_t)stream;
   const unsigned nb = grid_for(n, CS_THREADS * 64L, 512);
   const size_t lds = R <= CS_LDS_INTS ? (size_t)R * sizeof(int) : 0;
-  if (dtype == DT_F64)
-    hipLaunchKernelGGL(cs_ihist_kernel<double>, dim3(nb), dim3(CS_THREADS), lds, s, (const double*)X, ld, n, col, lo,
-                       R, counts);
-  else if (dtype == DT_F32)
-    hipLaunchKernelGGL(cs_ihist_kernel<float>, dim3(nb), dim3(CS_THREADS), lds, s, (const float*)X, ld, n, col, lo, R,
-                       counts);
-  else if (dtype == DT_I32)
-    hipLaunchKernelGGL(cs_ihist_kernel<int>, dim3(nb), dim3(CS_THREADS), lds, s, (const int*)X, ld, n, col, lo, R,
-                       counts);
-  else
-    return -1;
-  return (int)hipGetLastError();
+  return with_dtype<double, float, int>(dtype, [&](auto t) {
+    typedef typename decltype(t)::T T;
+    hipLaunchKernelGGL(cs_ihist_kernel<T>, dim3(nb), dim3(CS_THREADS), lds, s, (const T*)X, ld, n, col, lo, R, counts);
+    return (int)hipGetLastError();
+  });
 }
 
 // counts[d][L][V] (zeroed by the caller): X integer values in [vmin, vmin + V), label indices li
@@ -479,18 +470,14 @@ FMLX_API int fmlx_cs_hist(int dtype, const void* X, long ld, long n, int d, cons
   const uint64_t magic = d > 1 ? (uint64_t)((((unsigned __int128)1) << 64) / (unsigned)d) + 1 : 0;
   // privatised: enough blocks to fill the chip, each amortising its table over many elements
   const unsigned nb = grid_for(n * (long)d, CS_THREADS * 64L, priv ? 512 : 4096);
-#define FMLX_CS_HIST(T, P)                                                                                    \
-  hipLaunchKernelGGL((cs_hist_kernel<T, P>), dim3(nb), dim3(CS_THREADS), lds, s, (const T*)X, ld, n, d, li, L, \
-                     vmin, V, counts, magic, FS)
-  if (dtype == DT_F64) {
-    if (priv) FMLX_CS_HIST(double, true); else FMLX_CS_HIST(double, false);
-  } else if (dtype == DT_F32) {
-    if (priv) FMLX_CS_HIST(float, true); else FMLX_CS_HIST(float, false);
-  } else {
-    return -1;
-  }
-#undef FMLX_CS_HIST
-  return (int)hipGetLastError();
+  return with_dtype<double, float>(dtype, [&](auto t) {
+    typedef typename decltype(t)::T T;
+    return with_bool(priv, [&](auto pv) {
+      hipLaunchKernelGGL((cs_hist_kernel<T, pv.value>), dim3(nb), dim3(CS_THREADS), lds, s, (const T*)X, ld, n, d, li, L,
+                         vmin, V, counts, magic, FS);
+      return (int)hipGetLastError();
+    });
+  });
 }
 
 // keys / rows of columns [j0, j0 + nc) in column-major order (segment c = [c·n, (c+1)·n)) and the
@@ -500,15 +487,12 @@ FMLX_API int fmlx_cs_col_keys(int dtype, const void* X, long ld, long n, int j0,
   if (n >= (1L << 32)) return -2;
   hipStream_t s = (hipStream_t)stream;
   const unsigned nb = grid_for(n * (long)nc, CS_THREADS * 8L, 4096);
-  if (dtype == DT_F64)
-    hipLaunchKernelGGL(cs_col_keys_kernel<double>, dim3(nb), dim3(CS_THREADS), 0, s, (const double*)X, ld, n, j0, nc,
-                       keys, rows, orand);
-  else if (dtype == DT_F32)
-    hipLaunchKernelGGL(cs_col_keys_kernel<float>, dim3(nb), dim3(CS_THREADS), 0, s, (const float*)X, ld, n, j0, nc,
-                       keys, rows, orand);
-  else
-    return -1;
-  return (int)hipGetLastError();
+  return with_dtype<double, float>(dtype, [&](auto t) {
+    typedef typename decltype(t)::T T;
+    hipLaunchKernelGGL(cs_col_keys_kernel<T>, dim3(nb), dim3(CS_THREADS), 0, s, (const T*)X, ld, n, j0, nc, keys, rows,
+                       orand);
+    return (int)hipGetLastError();
+  });
 }
 
 // Distinct values of the sorted columns (keys / rows as sorted by fmlx_sort_u64, nc segments of n):

@@ -86,26 +86,6 @@ __global__ __launch_bounds__(256) void affine_cols_kernel(const T* __restrict__ 
   }
 }
 
-template <typename T>
-int launch_stats(const void* X, long ld, long n, int d, double* part, int nb, double* res, hipStream_t s) {
-  const long rpb = (n + nb - 1) / nb;
-  hipLaunchKernelGGL(colstats_partial_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)X, ld, n, d, rpb, part);
-  hipLaunchKernelGGL(colstats_combine_kernel, dim3((d + 255) / 256), dim3(256), 0, s, part, nb, d, res);
-  return (int)hipGetLastError();
-}
-
-template <typename T, typename O>
-int launch_affine(const void* X, long ld, long n, int d, const double* sub, const double* mul, const double* add,
-                  void* out, hipStream_t s) {
-  long total = n * (long)d;
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 8192) blocks = 8192;
-  if (blocks < 1) return 0;
-  hipLaunchKernelGGL((affine_cols_kernel<T, O>), dim3(blocks), dim3(256), 0, s, (const T*)X, ld, n, d, sub, mul, add,
-                     (O*)out);
-  return (int)hipGetLastError();
-}
-
 }  // namespace
 
 // part: scratch [nb][4][d] fp64; res: [4][d] fp64 = sum | sumsq | min | max
@@ -113,24 +93,38 @@ FMLX_API int fmlx_colstats(int dtype, const void* X, long ld, long n, int d, dou
                            void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (nb < 1) return -1;
-  if (dtype == DT_F32) return launch_stats<float>(X, ld, n, d, part, nb, res, s);
-  if (dtype == DT_F64) return launch_stats<double>(X, ld, n, d, part, nb, res, s);
-  if (dtype == DT_BF16) return launch_stats<bf16_t>(X, ld, n, d, part, nb, res, s);
-  return -1;
+  return with_dtype<float, double, bf16_t>(dtype, [&](auto t) {
+    typedef typename decltype(t)::T T;
+    const long rpb = (n + nb - 1) / nb;
+    hipLaunchKernelGGL(colstats_partial_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)X, ld, n, d, rpb, part);
+    hipLaunchKernelGGL(colstats_combine_kernel, dim3((d + 255) / 256), dim3(256), 0, s, part, nb, d, res);
+    return (int)hipGetLastError();
+  });
 }
 
-// out[r, c] = ((x - sub[c]) * mul[c]) + add[c]   (any of sub/mul/add may be null); out is dense [n, d]
+// out[r, c] = ((x - sub[c]) * mul[c]) + add[c]   (any of sub/mul/add may be null); out is dense [n, d].
+// (dtype, out_dtype): f32 → f32, f64 → f64, bf16 → f32, f32 → f64
 FMLX_API int fmlx_affine_cols(int dtype, int out_dtype, const void* X, long ld, long n, int d, const double* sub,
                               const double* mul, const double* add, void* out, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == DT_F32 && out_dtype == DT_F32) return launch_affine<float, float>(X, ld, n, d, sub, mul, add, out, s);
-  if (dtype == DT_F64 && out_dtype == DT_F64)
-    return launch_affine<double, double>(X, ld, n, d, sub, mul, add, out, s);
-  if (dtype == DT_BF16 && out_dtype == DT_F32)
-    return launch_affine<bf16_t, float>(X, ld, n, d, sub, mul, add, out, s);
-  if (dtype == DT_F32 && out_dtype == DT_F64)
-    return launch_affine<float, double>(X, ld, n, d, sub, mul, add, out, s);
-  return -1;
+  return with_dtype<float, double, bf16_t>(dtype, [&](auto ti) {
+    return with_dtype<float, double>(out_dtype, [&](auto to) {
+      typedef typename decltype(ti)::T T;
+      typedef typename decltype(to)::T O;
+      if constexpr (std::is_same<O, T>::value || (std::is_same<T, bf16_t>::value && std::is_same<O, float>::value) ||
+                    (std::is_same<T, float>::value && std::is_same<O, double>::value)) {
+        long total = n * (long)d;
+        int blocks = (int)((total + 255) / 256);
+        if (blocks > 8192) blocks = 8192;
+        if (blocks < 1) return 0;
+        hipLaunchKernelGGL((affine_cols_kernel<T, O>), dim3(blocks), dim3(256), 0, s, (const T*)X, ld, n, d, sub, mul,
+                           add, (O*)out);
+        return (int)hipGetLastError();
+      } else {
+        return -1;
+      }
+    });
+  });
 }
 
 // ---- Bucketizer (Bucketizer.java:118-143 with Bucketizer's binarySearch semantics): one pass

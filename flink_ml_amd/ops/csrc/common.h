@@ -19,6 +19,12 @@ typedef uint16_t bf16_t;
 
 // dtype codes shared with Python (flink_ml_amd/ops/native.py)
 enum FmlxDType { DT_F32 = 0, DT_F64 = 1, DT_BF16 = 2, DT_F16 = 3, DT_I32 = 4, DT_I64 = 5 };
+// ... and the C++ type each code stands for in a kernel's template arguments (with_dtype, dispatch.h)
+template <typename T> struct DTypeCode;
+template <> struct DTypeCode<float> { static constexpr int value = DT_F32; };
+template <> struct DTypeCode<double> { static constexpr int value = DT_F64; };
+template <> struct DTypeCode<bf16_t> { static constexpr int value = DT_BF16; };
+template <> struct DTypeCode<int> { static constexpr int value = DT_I32; };
 
 __device__ __forceinline__ float bf16_to_f32(bf16_t v) {
   return __uint_as_float(((uint32_t)v) << 16);
@@ -122,6 +128,8 @@ __device__ __forceinline__ void load_chunk_nt(const T* __restrict__ p, Chunk<T, 
 static inline int fmlx_ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
 #define FMLX_CHECK_LAUNCH() return (int)hipGetLastError()
+
+#include "dispatch.h"  // host side: run-time dtype / width arguments → template arguments
 
 // --- eager code-object loading ------------------------------------------------------------------
 // HIP loads a translation unit's code object lazily, at the first launch of any of its kernels

@@ -435,13 +435,12 @@ FMLX_API int fmlx_csc_fill(int f64, const int* order, long m, long j0, const int
                            void* evals, void* stream) {
   if (m <= 0) return 0;
   const dim3 g(grid_for(m, 256, 1u << 16));
-  if (f64)
-    hipLaunchKernelGGL(csc_fill_kernel<double>, g, dim3(256), 0, (hipStream_t)stream, order, m, j0, rel,
-                       (const double*)values, erow, (double*)evals);
-  else
-    hipLaunchKernelGGL(csc_fill_kernel<float>, g, dim3(256), 0, (hipStream_t)stream, order, m, j0, rel,
-                       (const float*)values, erow, (float*)evals);
-  return (int)hipGetLastError();
+  return with_acc(f64, [&](auto acc) {
+    typedef decltype(acc) A;
+    hipLaunchKernelGGL(csc_fill_kernel<A>, g, dim3(256), 0, (hipStream_t)stream, order, m, j0, rel, (const A*)values,
+                       erow, (A*)evals);
+    return (int)hipGetLastError();
+  });
 }
 
 // colptr: int32 [P, d + 1] of the whole partition; rows b0 … b0 + slots − 1 are written.
@@ -486,13 +485,12 @@ FMLX_API int fmlx_csc_tile_keys(int f64, const int* colptr, long b0, int slots, 
                                 int rb, int pb, int EL, uint64_t* keys, uint32_t* pay, void* stream) {
   if (slots <= 0 || rb < 1 || pb < 1 || rb + pb > 32) return -1;
   const dim3 g(tstride < 1024 ? tstride : 1024, slots);
-  if (f64)
-    hipLaunchKernelGGL(csc_tile_keys_kernel<double>, g, dim3(256), 0, (hipStream_t)stream, colptr, b0, d, (const int2*)tiles,
-                       tstride, ntiles, bstart, erow, (const double*)evals, j0, rb, pb, EL, keys, pay);
-  else
-    hipLaunchKernelGGL(csc_tile_keys_kernel<float>, g, dim3(256), 0, (hipStream_t)stream, colptr, b0, d, (const int2*)tiles,
-                       tstride, ntiles, bstart, erow, (const float*)evals, j0, rb, pb, EL, keys, pay);
-  return (int)hipGetLastError();
+  return with_acc(f64, [&](auto acc) {
+    typedef decltype(acc) A;
+    hipLaunchKernelGGL(csc_tile_keys_kernel<A>, g, dim3(256), 0, (hipStream_t)stream, colptr, b0, d, (const int2*)tiles,
+                       tstride, ntiles, bstart, erow, (const A*)evals, j0, rb, pb, EL, keys, pay);
+    return (int)hipGetLastError();
+  });
 }
 
 FMLX_API int fmlx_csc_tile_store(int f64, const uint64_t* keys, const uint32_t* pay, long m, long j0, int rb, int pb,
@@ -500,13 +498,12 @@ FMLX_API int fmlx_csc_tile_store(int f64, const uint64_t* keys, const uint32_t* 
   if (m <= 0) return 0;
   if (rb < 1 || pb < 1 || rb + pb > 32 || (f64 && src == nullptr)) return -1;
   const dim3 g(grid_for(m, 256, 1u << 16));
-  if (f64)
-    hipLaunchKernelGGL(csc_tile_store_kernel<double>, g, dim3(256), 0, (hipStream_t)stream, keys, pay, m, j0, rb, pb,
-                       (const double*)src, erow, (double*)evals);
-  else
-    hipLaunchKernelGGL(csc_tile_store_kernel<float>, g, dim3(256), 0, (hipStream_t)stream, keys, pay, m, j0, rb, pb,
-                       (const float*)nullptr, erow, (float*)evals);
-  return (int)hipGetLastError();
+  return with_acc(f64, [&](auto acc) {
+    typedef decltype(acc) A;  // src is read in fp64 only
+    hipLaunchKernelGGL(csc_tile_store_kernel<A>, g, dim3(256), 0, (hipStream_t)stream, keys, pay, m, j0, rb, pb,
+                       (const A*)(f64 ? src : nullptr), erow, (A*)evals);
+    return (int)hipGetLastError();
+  });
 }
 
 // Cells of the run's batches (see cell_keys_kernel): keys uint64 [m], pay uint32 [m] (m = j1 − j0).
@@ -536,13 +533,12 @@ FMLX_API int fmlx_cell_store(int f64, const uint64_t* keys, const uint32_t* pay,
   RunStarts rs{};
   for (int s = 0; s <= slots; ++s) rs.start[s] = (int)starts[s];
   const dim3 g(grid_for(m, 256, 1u << 16));
-  if (f64)
-    hipLaunchKernelGGL(cell_store_kernel<double>, g, dim3(256), 0, (hipStream_t)stream, keys, pay, m, j0, rs, slots,
-                       b0, roff, rstride, RBB, cb, (const double*)src, ent, (double*)val);
-  else
-    hipLaunchKernelGGL(cell_store_kernel<float>, g, dim3(256), 0, (hipStream_t)stream, keys, pay, m, j0, rs, slots, b0,
-                       roff, rstride, RBB, cb, (const float*)nullptr, ent, (float*)val);
-  return (int)hipGetLastError();
+  return with_acc(f64, [&](auto acc) {
+    typedef decltype(acc) A;  // src is read in fp64 only
+    hipLaunchKernelGGL(cell_store_kernel<A>, g, dim3(256), 0, (hipStream_t)stream, keys, pay, m, j0, rs, slots, b0, roff,
+                       rstride, RBB, cb, (const A*)(f64 ? src : nullptr), ent, (A*)val);
+    return (int)hipGetLastError();
+  });
 }
 
 // starts: HOST array of the run's batch starts relative to j0 (slots + 1 values)

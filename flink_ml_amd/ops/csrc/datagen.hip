@@ -315,16 +315,10 @@ FMLX_API int fmlx_java_rows(int vec_dtype, unsigned long long seed, unsigned lon
                             long nrows, const int* ops, const int* slot_off, int nslots, int nvec, int draws_per_row,
                             void* vec, double* scal, unsigned long long* first_reject, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (vec_dtype == DT_F64)
-    return launch<double>(seed, start_draw, row0, nrows, ops, slot_off, nslots, nvec, draws_per_row, vec, scal,
-                          first_reject, st);
-  if (vec_dtype == DT_F32)
-    return launch<float>(seed, start_draw, row0, nrows, ops, slot_off, nslots, nvec, draws_per_row, vec, scal,
-                         first_reject, st);
-  if (vec_dtype == DT_BF16)
-    return launch<bf16_t>(seed, start_draw, row0, nrows, ops, slot_off, nslots, nvec, draws_per_row, vec, scal,
-                          first_reject, st);
-  return -1;
+  return with_dtype<double, float, bf16_t>(vec_dtype, [&](auto t) {
+    return launch<typename decltype(t)::T>(seed, start_draw, row0, nrows, ops, slot_off, nslots, nvec, draws_per_row,
+                                           vec, scal, first_reject, st);
+  });
 }
 
 FMLX_DEFINE_PRELOAD()

@@ -351,42 +351,15 @@ FMLX_API int fmlx_dct_rows(const float* X, long rows, int n, const float* basis,
   if (grid > ntiles) grid = ntiles;
   const bool vec = (n % 4) == 0;
   hipStream_t s = (hipStream_t)stream;
-#define FMLX_DCT_LAUNCH(KSV, IV, VV)                                                                           \
-  hipLaunchKernelGGL((dct_rows_kernel<KSV, IV, VV>), dim3((unsigned)grid), dim3(DCT_THREADS), lds, s, X, rows, n, \
-                     basis, Y, g_dct_diag)
-#define FMLX_DCT_CASE(KSV)                              \
-  case KSV:                                             \
-    if (inverse) {                                      \
-      if (vec) FMLX_DCT_LAUNCH(KSV, true, true);        \
-      else FMLX_DCT_LAUNCH(KSV, true, false);           \
-    } else {                                            \
-      if (vec) FMLX_DCT_LAUNCH(KSV, false, true);       \
-      else FMLX_DCT_LAUNCH(KSV, false, false);          \
-    }                                                   \
-    break;
-  switch (g.KP / 4) {
-    FMLX_DCT_CASE(1)
-    FMLX_DCT_CASE(2)
-    FMLX_DCT_CASE(3)
-    FMLX_DCT_CASE(4)
-    FMLX_DCT_CASE(5)
-    FMLX_DCT_CASE(6)
-    FMLX_DCT_CASE(7)
-    FMLX_DCT_CASE(8)
-    FMLX_DCT_CASE(9)
-    FMLX_DCT_CASE(10)
-    FMLX_DCT_CASE(11)
-    FMLX_DCT_CASE(12)
-    FMLX_DCT_CASE(13)
-    FMLX_DCT_CASE(14)
-    FMLX_DCT_CASE(15)
-    FMLX_DCT_CASE(16)
-    default:
-      return -3;
-  }
-#undef FMLX_DCT_CASE
-#undef FMLX_DCT_LAUNCH
-  return (int)hipGetLastError();
+  return with_value<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>(g.KP / 4, [&](auto ks) {
+    return with_bool(inverse, [&](auto inv) {
+      return with_bool(vec, [&](auto v) {
+        hipLaunchKernelGGL((dct_rows_kernel<ks.value, inv.value, v.value>), dim3((unsigned)grid), dim3(DCT_THREADS),
+                           lds, s, X, rows, n, basis, Y, g_dct_diag);
+        return (int)hipGetLastError();
+      });
+    });
+  }, -3);
 }
 
 // fp64 rows (parity mode): Y = DCT-II / DCT-III of X, both double, basis as fmlx_dct_basis_shape
@@ -402,37 +375,13 @@ FMLX_API int fmlx_dct_rows_f64(const double* X, long rows, int n, const double* 
   long grid = (long)(num_cu > 0 ? num_cu : 256) * ((160 * 1024) / lds >= 2 ? 2 : 1);
   if (grid > ntiles) grid = ntiles;
   hipStream_t s = (hipStream_t)stream;
-#define FMLX_DCT64(KSV)                                                                                        \
-  case KSV:                                                                                                    \
-    if (inverse)                                                                                               \
-      hipLaunchKernelGGL((dct_rows_f64_kernel<KSV, true>), dim3((unsigned)grid), dim3(DCT_THREADS), lds, s, X, \
-                         rows, n, basis, Y);                                                                   \
-    else                                                                                                       \
-      hipLaunchKernelGGL((dct_rows_f64_kernel<KSV, false>), dim3((unsigned)grid), dim3(DCT_THREADS), lds, s, X, \
-                         rows, n, basis, Y);                                                                   \
-    break;
-  switch (g.KP / 4) {
-    FMLX_DCT64(1)
-    FMLX_DCT64(2)
-    FMLX_DCT64(3)
-    FMLX_DCT64(4)
-    FMLX_DCT64(5)
-    FMLX_DCT64(6)
-    FMLX_DCT64(7)
-    FMLX_DCT64(8)
-    FMLX_DCT64(9)
-    FMLX_DCT64(10)
-    FMLX_DCT64(11)
-    FMLX_DCT64(12)
-    FMLX_DCT64(13)
-    FMLX_DCT64(14)
-    FMLX_DCT64(15)
-    FMLX_DCT64(16)
-    default:
-      return -3;
-  }
-#undef FMLX_DCT64
-  return (int)hipGetLastError();
+  return with_value<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>(g.KP / 4, [&](auto ks) {
+    return with_bool(inverse, [&](auto inv) {
+      hipLaunchKernelGGL((dct_rows_f64_kernel<ks.value, inv.value>), dim3((unsigned)grid), dim3(DCT_THREADS), lds, s, X,
+                         rows, n, basis, Y);
+      return (int)hipGetLastError();
+    });
+  }, -3);
 }
 
 FMLX_DEFINE_PRELOAD()

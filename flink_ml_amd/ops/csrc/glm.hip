@@ -1563,32 +1563,17 @@ struct Layout {
   typedef T_ T;
   static constexpr int EPC = EPC_, CPL = CPL_;
 };
-template <typename T, int EPC, typename F>
-int with_cpl(int cpl, F&& f) {
-  switch (cpl) {
-    case 1: return f(Layout<T, EPC, 1>{});
-    case 2: return f(Layout<T, EPC, 2>{});
-    case 4: return f(Layout<T, EPC, 4>{});
-    case 8: return f(Layout<T, EPC, 8>{});
-  }
-  return -1;
-}
 template <typename F>
 int with_layout(int dtype, int epc, int cpl, F&& f) {
-  if (dtype == DT_BF16) {
-    if (epc == 8) return with_cpl<bf16_t, 8>(cpl, f);
-    if (epc == 4) return with_cpl<bf16_t, 4>(cpl, f);
-    if (epc == 2) return with_cpl<bf16_t, 2>(cpl, f);
-    if (epc == 1) return with_cpl<bf16_t, 1>(cpl, f);
-  } else if (dtype == DT_F32) {
-    if (epc == 4) return with_cpl<float, 4>(cpl, f);
-    if (epc == 2) return with_cpl<float, 2>(cpl, f);
-    if (epc == 1) return with_cpl<float, 1>(cpl, f);
-  } else if (dtype == DT_F64) {
-    if (epc == 2) return with_cpl<double, 2>(cpl, f);
-    if (epc == 1) return with_cpl<double, 1>(cpl, f);
-  }
-  return -1;
+  return with_dtype<bf16_t, float, double>(dtype, [&](auto t) {
+    typedef typename decltype(t)::T T;
+    return with_value<8, 4, 2, 1>(epc, [&](auto e) {
+      if constexpr (e.value * sizeof(T) <= 16)  // a chunk is one load: bf16 up to 8, fp32 4, fp64 2 elements
+        return with_value<1, 2, 4, 8>(cpl, [&](auto c) { return f(Layout<T, e.value, c.value>{}); });
+      else
+        return -1;
+    });
+  });
 }
 
 int launch_round(int dtype, int epc, int cpl, int u, const RoundArgs& a, const GlmTail& tl, int flags, hipStream_t s) {

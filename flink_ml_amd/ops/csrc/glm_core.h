@@ -137,10 +137,4 @@ __device__ __forceinline__ void arrive_and_advance(int* state, int e, bool cont,
 constexpr long LDS_PER_CU = 160 * 1024;
 constexpr int NUM_CU = 256;
 
-// host side: the accumulator type of an entry point's acc_f64 flag — f is called with a value of it
-template <typename F>
-int with_acc(int acc_f64, F&& f) {
-  return acc_f64 ? f(double{}) : f(float{});
-}
-
 }  // namespace

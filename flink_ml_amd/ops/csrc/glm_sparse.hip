@@ -1178,22 +1178,12 @@ __global__ __launch_bounds__(BK_NT) void glm_bkt_bwd_kernel(const long* __restri
   }
 }
 
-// the launch variants' visitors (the accumulator type: with_acc, glm_core.h): f is called with the
-// lane-group size / the flag as a compile-time constant; −1 for a group size no kernel has
+// the launch variants' visitors (the accumulator type and the flags: with_acc / with_bool,
+// dispatch.h): f is called with the lane-group size as a compile-time constant; −1 for a group
+// size no kernel has
 template <typename F>
 int with_group(int G, F&& f) {
-  switch (G) {
-    case 4: return f(std::integral_constant<int, 4>{});
-    case 8: return f(std::integral_constant<int, 8>{});
-    case 16: return f(std::integral_constant<int, 16>{});
-    case 32: return f(std::integral_constant<int, 32>{});
-    case 64: return f(std::integral_constant<int, 64>{});
-    default: return -1;
-  }
-}
-template <typename F>
-int with_flag(int on, F&& f) {
-  return on ? f(std::true_type{}) : f(std::false_type{});
+  return with_value<4, 8, 16, 32, 64>(G, f);
 }
 
 }  // namespace
@@ -1285,7 +1275,7 @@ static int launch_csc_round(const SparseRound& r, void* mult, const int* colptr,
                        (A*)mult, (A*)r.wl);
   }
   const int weighted = r.wt != nullptr;
-  return with_flag(r.fuse, [&](auto fuse) {
+  return with_bool(r.fuse, [&](auto fuse) {
     constexpr bool F = decltype(fuse)::value;
     if (ti.tiles != nullptr) {
       const size_t lds = (size_t)ti.ET * sizeof(A);
@@ -1404,7 +1394,7 @@ static int launch_bkt_round(const SparseRound& r, const BktArgs& k, int bwd_bloc
                      r.indptr, r.idx, (const A*)r.val, (const A*)r.y, (const A*)r.wt, (const A*)r.coef, r.n, r.B,
                      r.loss, r.state, (A*)r.wl, k, g_bkt_trace, g_bkt_trace_blocks);
   const int weighted = r.wt != nullptr;
-  return with_flag(r.fuse, [&](auto fuse) {
+  return with_bool(r.fuse, [&](auto fuse) {
     hipLaunchKernelGGL((glm_bkt_bwd_kernel<A, decltype(fuse)::value>), dim3(bwd_blocks), dim3(BK_NT),
                        bkt_bwd_lds(k, sizeof(A)), s, r.indptr, r.n, r.d, r.B, r.state, (A*)r.wl, (A*)r.fb, (A*)r.coef,
                        r.max_iter, (A)r.tol, (A)r.lr, (A)r.reg, (A)r.en, weighted, k);
@@ -1500,7 +1490,7 @@ FMLX_API int fmlx_glm_sparse_warm(void* stream) {
           return 0;
         });
       for (int fuse = 0; fuse < 2; ++fuse)
-        with_flag(fuse, [&](auto f) {
+        with_bool(fuse, [&](auto f) {
           hipLaunchKernelGGL((glm_bkt_bwd_kernel<A, decltype(f)::value>), dim3(1), dim3(BK_NT), 1024, s, ip, 1L, 1, 1L,
                              st, (A*)wls, (A*)scratch, (A*)scratch, 1, (A)0, (A)0, (A)0, (A)0, 0, k);
           return 0;

@@ -96,10 +96,8 @@ FMLX_API int fmlx_group_colstats(int dtype, const void* X, long ld, long n, int 
                                  const double* w, double* part, int nb, double* res, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (G < 1 || G > kMaxGroups || nb < 1 || d < 1) return -1;
-  if (dtype == DT_F32) return launch<float>(X, ld, n, d, gidx, G, w, part, nb, res, s);
-  if (dtype == DT_F64) return launch<double>(X, ld, n, d, gidx, G, w, part, nb, res, s);
-  if (dtype == DT_BF16) return launch<bf16_t>(X, ld, n, d, gidx, G, w, part, nb, res, s);
-  return -1;
+  return with_dtype<float, double, bf16_t>(
+      dtype, [&](auto t) { return launch<typename decltype(t)::T>(X, ld, n, d, gidx, G, w, part, nb, res, s); });
 }
 
 FMLX_DEFINE_PRELOAD()

@@ -994,33 +994,17 @@ int launch_assign_bf16(const void* X, long ld, long n, int D, const void* Cb, co
       return (int)hipGetLastError();
     }
   }
-  if (full)
-    hipLaunchKernelGGL((kmeans_assign_bf16_kernel<KS, true>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)X, ld, n, D,
-                       (const bf16_t*)Cb, cnorm, kpad, labels);
-  else
-    hipLaunchKernelGGL((kmeans_assign_bf16_kernel<KS, false>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)X, ld, n,
+  return with_bool(full, [&](auto fl) {
+    hipLaunchKernelGGL((kmeans_assign_bf16_kernel<KS, fl.value>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)X, ld, n,
                        D, (const bf16_t*)Cb, cnorm, kpad, labels);
-  return (int)hipGetLastError();
+    return (int)hipGetLastError();
+  });
 }
 
-template <typename T, int VPL>
-int launch_chunk_sum(const void* X, long ld, int D, const long* order, const long* offsets, const long* chunk_off,
-                     int k, long max_chunks, void* partial, hipStream_t s) {
-  if (max_chunks <= 0) return 0;
-  hipLaunchKernelGGL((kmeans_chunk_sum_kernel<T, VPL>), dim3((unsigned)max_chunks), dim3(256), 0, s, (const T*)X, ld,
-                     D, order, offsets, chunk_off, k, (typename AccOf<T>::type*)partial);
-  return (int)hipGetLastError();
-}
-
-template <typename T>
-int chunk_sum_vpl(const void* X, long ld, int D, const long* order, const long* offsets, const long* chunk_off, int k,
-                  long max_chunks, void* partial, hipStream_t s) {
-  if (D <= 64) return launch_chunk_sum<T, 1>(X, ld, D, order, offsets, chunk_off, k, max_chunks, partial, s);
-  if (D <= 128) return launch_chunk_sum<T, 2>(X, ld, D, order, offsets, chunk_off, k, max_chunks, partial, s);
-  if (D <= 256) return launch_chunk_sum<T, 4>(X, ld, D, order, offsets, chunk_off, k, max_chunks, partial, s);
-  if (D <= 512) return launch_chunk_sum<T, 8>(X, ld, D, order, offsets, chunk_off, k, max_chunks, partial, s);
-  if (D <= 1024) return launch_chunk_sum<T, 16>(X, ld, D, order, offsets, chunk_off, k, max_chunks, partial, s);
-  return -3;
+// values per lane of the wave-per-row kernels: D <= 64 / 128 / 256 / 512 / 1024 → VPL 1 / 2 / 4 / 8 / 16
+template <typename F>
+int with_vpl(int D, F&& f, int miss) {
+  return with_ceil<1, 2, 4, 8, 16>(fmlx_ceil_div(D, 64), f, miss);
 }
 
 }  // namespace
@@ -1038,78 +1022,56 @@ FMLX_API int fmlx_kmeans_assign_bf16(const void* X, long ld, long n, int D, int 
                                      int kpad, int* labels, void* baug, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (KS * 16 < D) return -2;
-  switch (KS) {
-    case 1: return launch_assign_bf16<1>(X, ld, n, D, Cb, cnorm, kpad, labels, baug, s);
-    case 2: return launch_assign_bf16<2>(X, ld, n, D, Cb, cnorm, kpad, labels, baug, s);
-    case 3: return launch_assign_bf16<3>(X, ld, n, D, Cb, cnorm, kpad, labels, baug, s);
-    case 4: return launch_assign_bf16<4>(X, ld, n, D, Cb, cnorm, kpad, labels, baug, s);
-    case 5: return launch_assign_bf16<5>(X, ld, n, D, Cb, cnorm, kpad, labels, baug, s);
-    case 6: return launch_assign_bf16<6>(X, ld, n, D, Cb, cnorm, kpad, labels, baug, s);
-    case 7: return launch_assign_bf16<7>(X, ld, n, D, Cb, cnorm, kpad, labels, baug, s);
-    case 8: return launch_assign_bf16<8>(X, ld, n, D, Cb, cnorm, kpad, labels, baug, s);
-    case 10: return launch_assign_bf16<10>(X, ld, n, D, Cb, cnorm, kpad, labels, baug, s);
-    case 12: return launch_assign_bf16<12>(X, ld, n, D, Cb, cnorm, kpad, labels, baug, s);
-    case 16: return launch_assign_bf16<16>(X, ld, n, D, Cb, cnorm, kpad, labels, baug, s);
-  }
-  return -2;  // unsupported D for the MFMA path
-}
-
-template <typename T, int VPL>
-int launch_assign_wave(const void* X, long ld, long n, int D, const void* C, const void* cnrm, int k, int metric,
-                       int* labels, hipStream_t s) {
-  const size_t need = ((size_t)k * D + k) * sizeof(T);
-  const int use_lds = need <= 64 * 1024;
-  const size_t sh = use_lds ? need : 0;
-  long waves = n;
-  long blocks = (waves + 3) / 4;
-  if (blocks > 2048) blocks = 2048;  // ≫ 256 CUs; each wave then loops over rows
-  hipLaunchKernelGGL((kmeans_assign_wave_kernel<T, VPL>), dim3((unsigned)blocks), dim3(256), sh, s, (const T*)X, ld,
-                     n, D, (const T*)C, (const T*)cnrm, k, metric, use_lds, labels);
-  return (int)hipGetLastError();
-}
-
-template <typename T>
-int assign_wave_vpl(const void* X, long ld, long n, int D, const void* C, const void* cnrm, int k, int metric,
-                    int* labels, hipStream_t s) {
-  if (D <= 64) return launch_assign_wave<T, 1>(X, ld, n, D, C, cnrm, k, metric, labels, s);
-  if (D <= 128) return launch_assign_wave<T, 2>(X, ld, n, D, C, cnrm, k, metric, labels, s);
-  if (D <= 256) return launch_assign_wave<T, 4>(X, ld, n, D, C, cnrm, k, metric, labels, s);
-  if (D <= 512) return launch_assign_wave<T, 8>(X, ld, n, D, C, cnrm, k, metric, labels, s);
-  return launch_assign_wave<T, 16>(X, ld, n, D, C, cnrm, k, metric, labels, s);
+  return with_value<1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 16>(
+      KS, [&](auto ks) { return launch_assign_bf16<ks.value>(X, ld, n, D, Cb, cnorm, kpad, labels, baug, s); },
+      -2);  // unsupported D for the MFMA path
 }
 
 FMLX_API int fmlx_kmeans_assign_generic(int dtype, const void* X, long ld, long n, int D, const void* C,
                                         const void* cnrm, int k, int metric, int* labels, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (n == 0) return 0;
-  if (D <= 1024) {
-    if (dtype == DT_F64) return assign_wave_vpl<double>(X, ld, n, D, C, cnrm, k, metric, labels, s);
-    if (dtype == DT_F32) return assign_wave_vpl<float>(X, ld, n, D, C, cnrm, k, metric, labels, s);
-    return -1;
-  }
-  const int blocks = (int)((n + 255) / 256);
-  const size_t es = dtype == DT_F64 ? 8 : 4;
-  const size_t need = (size_t)k * D * es;
-  const int use_lds = need <= 64 * 1024;
-  const size_t sh = use_lds ? need : 0;
-  if (dtype == DT_F64)
-    hipLaunchKernelGGL(kmeans_assign_generic_kernel<double>, dim3(blocks), dim3(256), sh, s, (const double*)X, ld, n,
-                       D, (const double*)C, (const double*)cnrm, k, metric, use_lds, labels);
-  else if (dtype == DT_F32)
-    hipLaunchKernelGGL(kmeans_assign_generic_kernel<float>, dim3(blocks), dim3(256), sh, s, (const float*)X, ld, n, D,
-                       (const float*)C, (const float*)cnrm, k, metric, use_lds, labels);
-  else
-    return -1;
-  return (int)hipGetLastError();
+  if (D <= 1024)  // a wave per row
+    return with_dtype<double, float>(dtype, [&](auto t) {
+      typedef typename decltype(t)::T T;
+      const size_t need = ((size_t)k * D + k) * sizeof(T);
+      const int use_lds = need <= 64 * 1024;
+      const size_t sh = use_lds ? need : 0;
+      long waves = n;
+      long blocks = (waves + 3) / 4;
+      if (blocks > 2048) blocks = 2048;  // ≫ 256 CUs; each wave then loops over rows
+      return with_vpl(D, [&](auto vpl) {
+        hipLaunchKernelGGL((kmeans_assign_wave_kernel<T, vpl.value>), dim3((unsigned)blocks), dim3(256), sh, s,
+                           (const T*)X, ld, n, D, (const T*)C, (const T*)cnrm, k, metric, use_lds, labels);
+        return (int)hipGetLastError();
+      }, -1);
+    });
+  return with_dtype<double, float>(dtype, [&](auto t) {  // a thread per row
+    typedef typename decltype(t)::T T;
+    const int blocks = (int)((n + 255) / 256);
+    const size_t need = (size_t)k * D * sizeof(T);
+    const int use_lds = need <= 64 * 1024;
+    const size_t sh = use_lds ? need : 0;
+    hipLaunchKernelGGL(kmeans_assign_generic_kernel<T>, dim3(blocks), dim3(256), sh, s, (const T*)X, ld, n, D,
+                       (const T*)C, (const T*)cnrm, k, metric, use_lds, labels);
+    return (int)hipGetLastError();
+  });
 }
 
+// −3: rows wider than 1024 (VPL 16)
 FMLX_API int fmlx_kmeans_chunk_sum(int dtype, const void* X, long ld, int D, const long* order, const long* offsets,
                                    const long* chunk_off, int k, long max_chunks, void* partial, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == DT_BF16) return chunk_sum_vpl<bf16_t>(X, ld, D, order, offsets, chunk_off, k, max_chunks, partial, s);
-  if (dtype == DT_F32) return chunk_sum_vpl<float>(X, ld, D, order, offsets, chunk_off, k, max_chunks, partial, s);
-  if (dtype == DT_F64) return chunk_sum_vpl<double>(X, ld, D, order, offsets, chunk_off, k, max_chunks, partial, s);
-  return -1;
+  return with_dtype<bf16_t, float, double>(dtype, [&](auto t) {
+    typedef typename decltype(t)::T T;
+    typedef typename decltype(t)::A A;
+    return with_vpl(D, [&](auto vpl) {
+      if (max_chunks <= 0) return 0;
+      hipLaunchKernelGGL((kmeans_chunk_sum_kernel<T, vpl.value>), dim3((unsigned)max_chunks), dim3(256), 0, s,
+                         (const T*)X, ld, D, order, offsets, chunk_off, k, (A*)partial);
+      return (int)hipGetLastError();
+    }, -3);
+  });
 }
 
 // bf16 fast path of the centroid accumulation: int32 row order (from the radix sort),
@@ -1120,19 +1082,11 @@ FMLX_API int fmlx_kmeans_chunk_sum_bf16v(const void* X, long ld, int D, const in
   hipStream_t s = (hipStream_t)stream;
   if (max_chunks <= 0) return 0;
   if ((ld % 8) != 0 || ((uintptr_t)X % 16) != 0) return -2;
-  dim3 g((unsigned)max_chunks);
-  const bf16_t* x = (const bf16_t*)X;
-  switch (D) {
-    case 8: hipLaunchKernelGGL(kmeans_chunk_sum_bf16v_kernel<1>, g, dim3(256), 0, s, x, ld, D, order, offsets, chunk_off, k, partial); break;
-    case 16: hipLaunchKernelGGL(kmeans_chunk_sum_bf16v_kernel<2>, g, dim3(256), 0, s, x, ld, D, order, offsets, chunk_off, k, partial); break;
-    case 32: hipLaunchKernelGGL(kmeans_chunk_sum_bf16v_kernel<4>, g, dim3(256), 0, s, x, ld, D, order, offsets, chunk_off, k, partial); break;
-    case 64: hipLaunchKernelGGL(kmeans_chunk_sum_bf16v_kernel<8>, g, dim3(256), 0, s, x, ld, D, order, offsets, chunk_off, k, partial); break;
-    case 128: hipLaunchKernelGGL(kmeans_chunk_sum_bf16v_kernel<16>, g, dim3(256), 0, s, x, ld, D, order, offsets, chunk_off, k, partial); break;
-    case 256: hipLaunchKernelGGL(kmeans_chunk_sum_bf16v_kernel<32>, g, dim3(256), 0, s, x, ld, D, order, offsets, chunk_off, k, partial); break;
-    case 512: hipLaunchKernelGGL(kmeans_chunk_sum_bf16v_kernel<64>, g, dim3(256), 0, s, x, ld, D, order, offsets, chunk_off, k, partial); break;
-    default: return -2;
-  }
-  return (int)hipGetLastError();
+  return with_value<1, 2, 4, 8, 16, 32, 64>(D % 8 ? 0 : D / 8, [&](auto lpr) {
+    hipLaunchKernelGGL(kmeans_chunk_sum_bf16v_kernel<lpr.value>, dim3((unsigned)max_chunks), dim3(256), 0, s,
+                       (const bf16_t*)X, ld, D, order, offsets, chunk_off, k, partial);
+    return (int)hipGetLastError();
+  }, -2);
 }
 
 FMLX_API int fmlx_kmeans_offsets(const int* keys_sorted, long n, int k, long* offsets, long* chunk_off, void* stream) {
@@ -1145,25 +1099,23 @@ FMLX_API int fmlx_kmeans_cluster_sum(int acc_f64, const void* partial, int D, co
                                      const long* chunk_off, int k, void* out, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(k, (D + 255) / 256);
-  if (acc_f64)
-    hipLaunchKernelGGL(kmeans_cluster_sum_kernel<double>, grid, dim3(256), 0, s, (const double*)partial, D, offsets,
-                       chunk_off, k, (double*)out);
-  else
-    hipLaunchKernelGGL(kmeans_cluster_sum_kernel<float>, grid, dim3(256), 0, s, (const float*)partial, D, offsets,
-                       chunk_off, k, (float*)out);
-  return (int)hipGetLastError();
+  return with_acc(acc_f64, [&](auto acc) {
+    typedef decltype(acc) A;
+    hipLaunchKernelGGL(kmeans_cluster_sum_kernel<A>, grid, dim3(256), 0, s, (const A*)partial, D, offsets, chunk_off,
+                       k, (A*)out);
+    return (int)hipGetLastError();
+  });
 }
 
 FMLX_API int fmlx_kmeans_finalize(int acc_f64, const void* red, int D, int k, void* cent, double* weights, void* Cb,
                                   int DP, float* cnorm_bf16, void* cnorm_acc, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (acc_f64)
-    hipLaunchKernelGGL(kmeans_finalize_kernel<double>, dim3(k), dim3(256), 0, s, (const double*)red, D, k,
-                       (double*)cent, weights, (bf16_t*)Cb, DP, cnorm_bf16, (double*)cnorm_acc);
-  else
-    hipLaunchKernelGGL(kmeans_finalize_kernel<float>, dim3(k), dim3(256), 0, s, (const float*)red, D, k, (float*)cent,
-                       weights, (bf16_t*)Cb, DP, cnorm_bf16, (float*)cnorm_acc);
-  return (int)hipGetLastError();
+  return with_acc(acc_f64, [&](auto acc) {
+    typedef decltype(acc) A;
+    hipLaunchKernelGGL(kmeans_finalize_kernel<A>, dim3(k), dim3(256), 0, s, (const A*)red, D, k, (A*)cent, weights,
+                       (bf16_t*)Cb, DP, cnorm_bf16, (A*)cnorm_acc);
+    return (int)hipGetLastError();
+  });
 }
 
 FMLX_DEFINE_PRELOAD()

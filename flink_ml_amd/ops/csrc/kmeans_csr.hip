@@ -132,26 +132,17 @@ int kc_launch_assign(const long* indptr, const int* idx, const void* val, long n
                      const void* norms, int metric, int* labels, int* err, hipStream_t s) {
   long blocks = (n + 3) / 4;
   if (blocks > 8192) blocks = 8192;
-  if (metric == 1)
-    hipLaunchKernelGGL((kmeans_csr_assign_kernel<T, NA, true>), dim3((unsigned)blocks), dim3(256), 0, s, indptr, idx,
-                       (const T*)val, n, D, (const T*)Ct, kp, k, (const T*)norms, metric, labels, err);
-  else
-    hipLaunchKernelGGL((kmeans_csr_assign_kernel<T, NA, false>), dim3((unsigned)blocks), dim3(256), 0, s, indptr, idx,
-                       (const T*)val, n, D, (const T*)Ct, kp, k, (const T*)norms, metric, labels, err);
-  return (int)hipGetLastError();
+  return with_bool(metric == 1, [&](auto cosine) {
+    hipLaunchKernelGGL((kmeans_csr_assign_kernel<T, NA, cosine.value>), dim3((unsigned)blocks), dim3(256), 0, s, indptr,
+                       idx, (const T*)val, n, D, (const T*)Ct, kp, k, (const T*)norms, metric, labels, err);
+    return (int)hipGetLastError();
+  });
 }
 
-template <typename T>
-int kc_assign_na(const long* indptr, const int* idx, const void* val, long n, int D, const void* Ct, int kp, int k,
-                 const void* norms, int metric, int* labels, int* err, hipStream_t s) {
-  switch (kp <= 64 ? 1 : kp / 64) {
-    case 1: return kc_launch_assign<T, 1>(indptr, idx, val, n, D, Ct, kp, k, norms, metric, labels, err, s);
-    case 2: return kc_launch_assign<T, 2>(indptr, idx, val, n, D, Ct, kp, k, norms, metric, labels, err, s);
-    case 4: return kc_launch_assign<T, 4>(indptr, idx, val, n, D, Ct, kp, k, norms, metric, labels, err, s);
-    case 8: return kc_launch_assign<T, 8>(indptr, idx, val, n, D, Ct, kp, k, norms, metric, labels, err, s);
-    case 16: return kc_launch_assign<T, 16>(indptr, idx, val, n, D, Ct, kp, k, norms, metric, labels, err, s);
-  }
-  return -1;
+// accumulators per lane: one up to kp = 64, then kp / 64 (kp a power of two <= 1024: kc_kp_ok)
+template <typename F>
+int with_na(int kp, F&& f) {
+  return with_value<1, 2, 4, 8, 16>(kp <= 64 ? 1 : kp / 64, f);
 }
 
 // kp is a power of two <= 64 or 64 * {1, 2, 4, 8, 16}, and holds k
@@ -359,24 +350,6 @@ int kc_launch_colsum(const long* colptr, const int* crow, const void* cval, cons
   return (int)hipGetLastError();
 }
 
-template <typename T>
-int kc_colsum_na(const long* colptr, const int* crow, const void* cval, const int* labels, long n, int D, int kp, int k,
-                 long seg, int nlong, const int* long_col, const long* long_seg0, long nsegs, const int* seg_col,
-                 const int* seg_k, void* partial, int* counts, void* payload, hipStream_t s) {
-#define KC_COLSUM(NA)                                                                                             \
-  return kc_launch_colsum<T, NA>(colptr, crow, cval, labels, n, D, kp, k, seg, nlong, long_col, long_seg0, nsegs, \
-                                 seg_col, seg_k, partial, counts, payload, s)
-  switch (kp <= 64 ? 1 : kp / 64) {
-    case 1: KC_COLSUM(1);
-    case 2: KC_COLSUM(2);
-    case 4: KC_COLSUM(4);
-    case 8: KC_COLSUM(8);
-    case 16: KC_COLSUM(16);
-  }
-#undef KC_COLSUM
-  return -1;
-}
-
 // ------------------------------------------------------------------------------------------
 // finalize
 // ------------------------------------------------------------------------------------------
@@ -447,16 +420,6 @@ __global__ __launch_bounds__(256) void kmeans_csr_norms_kernel(const T* __restri
   if (t < k) weights[t] = (double)red[(long)D * kp + t];
 }
 
-template <typename T>
-int kc_launch_finalize(const void* red, int D, int kp, int k, void* Ct, void* norms, double* weights, void* part,
-                       int rpb, int nb, hipStream_t s) {
-  hipLaunchKernelGGL(kmeans_csr_finalize_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)red, D, kp, k, rpb, (T*)Ct,
-                     (T*)part);
-  hipLaunchKernelGGL(kmeans_csr_norms_kernel<T>, dim3((kp + 255) / 256), dim3(256), 0, s, (const T*)red, D, kp, k, nb,
-                     (const T*)part, (T*)norms, weights);
-  return (int)hipGetLastError();
-}
-
 }  // namespace
 
 FMLX_API int fmlx_kmeans_csr_assign(int f64, const long* indptr, const int* idx, const void* val, long n, int D,
@@ -465,8 +428,11 @@ FMLX_API int fmlx_kmeans_csr_assign(int f64, const long* indptr, const int* idx,
   hipStream_t s = (hipStream_t)stream;
   if (n <= 0) return 0;
   if (!kc_kp_ok(kp, k) || D < 1 || metric < 0 || metric > 2) return -1;
-  if (f64) return kc_assign_na<double>(indptr, idx, val, n, D, Ct, kp, k, norms, metric, labels, err, s);
-  return kc_assign_na<float>(indptr, idx, val, n, D, Ct, kp, k, norms, metric, labels, err, s);
+  return with_acc(f64, [&](auto acc) {
+    return with_na(kp, [&](auto na) {
+      return kc_launch_assign<decltype(acc), na.value>(indptr, idx, val, n, D, Ct, kp, k, norms, metric, labels, err, s);
+    });
+  });
 }
 
 // sort keys / entry ids / rows of the partition's entries (nnz = indptr[n] < 2^31)
@@ -491,13 +457,12 @@ FMLX_API int fmlx_kmeans_csr_gather(int f64, const int* order, const int* erow, 
                                     void* cval, void* stream) {
   if (nnz <= 0) return 0;
   const dim3 grid((unsigned)((nnz + 255) / 256));
-  if (f64)
-    hipLaunchKernelGGL(kmeans_csr_gather_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, order, erow,
-                       (const double*)val, nnz, crow, (double*)cval);
-  else
-    hipLaunchKernelGGL(kmeans_csr_gather_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, order, erow,
-                       (const float*)val, nnz, crow, (float*)cval);
-  return (int)hipGetLastError();
+  return with_acc(f64, [&](auto acc) {
+    typedef decltype(acc) T;
+    hipLaunchKernelGGL(kmeans_csr_gather_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, order, erow, (const T*)val,
+                       nnz, crow, (T*)cval);
+    return (int)hipGetLastError();
+  });
 }
 
 // payload = [St[D][kp] | k counts]; columns longer than seg entries go through the segment table
@@ -508,11 +473,12 @@ FMLX_API int fmlx_kmeans_csr_colsum(int f64, const long* colptr, const int* crow
                                     void* partial, int* counts, void* payload, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (!kc_kp_ok(kp, k) || D < 1 || seg < 1 || n < 0) return -1;
-  if (f64)
-    return kc_colsum_na<double>(colptr, crow, cval, labels, n, D, kp, k, seg, nlong, long_col, long_seg0, nsegs, seg_col,
-                                seg_k, partial, counts, payload, s);
-  return kc_colsum_na<float>(colptr, crow, cval, labels, n, D, kp, k, seg, nlong, long_col, long_seg0, nsegs, seg_col,
-                             seg_k, partial, counts, payload, s);
+  return with_acc(f64, [&](auto acc) {
+    return with_na(kp, [&](auto na) {
+      return kc_launch_colsum<decltype(acc), na.value>(colptr, crow, cval, labels, n, D, kp, k, seg, nlong, long_col,
+                                                       long_seg0, nsegs, seg_col, seg_k, partial, counts, payload, s);
+    });
+  });
 }
 
 // part: nb blocks x 2 x kp partial norms, nb = ceil(D / rpb)
@@ -520,8 +486,14 @@ FMLX_API int fmlx_kmeans_csr_finalize(int f64, const void* payload, int D, int k
                                       double* weights, void* part, int rpb, int nb, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (!kc_kp_ok(kp, k) || D < 1 || rpb < 1 || (long)nb * rpb < D || (long)(nb - 1) * rpb >= D) return -1;
-  if (f64) return kc_launch_finalize<double>(payload, D, kp, k, Ct, norms, weights, part, rpb, nb, s);
-  return kc_launch_finalize<float>(payload, D, kp, k, Ct, norms, weights, part, rpb, nb, s);
+  return with_acc(f64, [&](auto acc) {
+    typedef decltype(acc) T;
+    hipLaunchKernelGGL(kmeans_csr_finalize_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)payload, D, kp, k, rpb,
+                       (T*)Ct, (T*)part);
+    hipLaunchKernelGGL(kmeans_csr_norms_kernel<T>, dim3((kp + 255) / 256), dim3(256), 0, s, (const T*)payload, D, kp, k,
+                       nb, (const T*)part, (T*)norms, weights);
+    return (int)hipGetLastError();
+  });
 }
 
 FMLX_DEFINE_PRELOAD()

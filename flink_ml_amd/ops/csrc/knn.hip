@@ -219,12 +219,11 @@ int launch_topk(const float* G, long ldg, long nq, long n, int S, const float* q
   const bool vec = (n % 4 == 0) && (ldg % 4 == 0) && ((uintptr_t)G % 16 == 0) && ((uintptr_t)tn % 16 == 0);
   int* si = S > 1 ? ws_i : idx;
   float* sd = S > 1 ? ws_d : dist;
-  if (vec)
-    hipLaunchKernelGGL((knn_topk_scan_kernel<K, true>), dim3(blocks, S), dim3(256), 0, s, G, ldg, nq, n, S, qn, tn,
+  with_bool(vec, [&](auto v) {
+    hipLaunchKernelGGL((knn_topk_scan_kernel<K, v.value>), dim3(blocks, S), dim3(256), 0, s, G, ldg, nq, n, S, qn, tn,
                        k, si, sd);
-  else
-    hipLaunchKernelGGL((knn_topk_scan_kernel<K, false>), dim3(blocks, S), dim3(256), 0, s, G, ldg, nq, n, S, qn, tn,
-                       k, si, sd);
+    return 0;
+  });
   if (S > 1)
     hipLaunchKernelGGL((knn_topk_merge_kernel<K>), dim3(blocks), dim3(256), 0, s, ws_d, ws_i, nq, S, k, idx, dist);
   FMLX_CHECK_LAUNCH();
@@ -463,12 +462,15 @@ int launch_fused(const float* Q, long ldq, long nq, int D, const float* Tt, long
   FMLX_CHECK_LAUNCH();
 }
 
-template <int K>
-int launch_fused_k(const float* Q, long ldq, long nq, int D, const float* Tt, long n, int dp, int k, int S, int* idx,
-                   float* dist, float* ws_d, int* ws_i, hipStream_t s) {
-  if (dp <= 16) return launch_fused<K, 16>(Q, ldq, nq, D, Tt, n, dp, k, S, idx, dist, ws_d, ws_i, s);
-  if (dp <= 32) return launch_fused<K, 32>(Q, ldq, nq, D, Tt, n, dp, k, S, idx, dist, ws_d, ws_i, s);
-  return launch_fused<K, 64>(Q, ldq, nq, D, Tt, n, dp, k, S, idx, dist, ws_d, ws_i, s);
+// The one map from (k, dp) to the fused kernel's <K, DPMAX>: K the list length (k rounded up to
+// 4 / 8 / 16 / 32 / 64), DPMAX the ceiling of dp (16 / 32 / 64). Both the launcher and the
+// occupancy query go through it. The last rung of each ladder takes whatever is left (the launcher
+// has validated k <= 64 and dp <= 64 before; the query answers for any pair).
+template <typename F>
+int with_fused_shape(int k, int dp, F&& f) {
+  return with_ceil<4, 8, 16, 32, 64>(k < 64 ? k : 64, [&](auto K) {
+    return with_ceil<16, 32, 64>(dp < 64 ? dp : 64, [&](auto DPMAX) { return f(K, DPMAX); });
+  });
 }
 
 }  // namespace
@@ -487,12 +489,8 @@ FMLX_API int fmlx_knn_topk(const float* G, long ldg, long nq, long n, int S, con
   if (k < 1 || k > 32 || k > n || n >= (long)INT32_MAX || ldg < n || S < 1 || S > 256) return -1;
   if (S > 1 && (ws_d == nullptr || ws_i == nullptr)) return -1;
   if (nq == 0) return 0;
-  if (k <= 1) return launch_topk<1>(G, ldg, nq, n, S, qn, tn, k, idx, dist, ws_d, ws_i, s);
-  if (k <= 2) return launch_topk<2>(G, ldg, nq, n, S, qn, tn, k, idx, dist, ws_d, ws_i, s);
-  if (k <= 4) return launch_topk<4>(G, ldg, nq, n, S, qn, tn, k, idx, dist, ws_d, ws_i, s);
-  if (k <= 8) return launch_topk<8>(G, ldg, nq, n, S, qn, tn, k, idx, dist, ws_d, ws_i, s);
-  if (k <= 16) return launch_topk<16>(G, ldg, nq, n, S, qn, tn, k, idx, dist, ws_d, ws_i, s);
-  return launch_topk<32>(G, ldg, nq, n, S, qn, tn, k, idx, dist, ws_d, ws_i, s);
+  return with_ceil<1, 2, 4, 8, 16, 32>(
+      k, [&](auto K) { return launch_topk<K.value>(G, ldg, nq, n, S, qn, tn, k, idx, dist, ws_d, ws_i, s); });
 }
 
 // Fused KNN: Q [nq, D] fp32 (leading dim ldq); training points pre-arranged as ceil(n/64) tiles
@@ -502,28 +500,14 @@ FMLX_API int fmlx_knn_topk(const float* G, long ldg, long nq, long n, int S, con
 // if non-null, dist [nq, k]. S training segments (1..256); S > 1 needs ws_d/ws_i of nq·S·k.
 FMLX_API int fmlx_knn_fused_max_k() { return 64; }
 
-namespace {
-template <int K, int DPMAX>
-int fused_blocks_per_cu() {
-  int b = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, knn_fused_kernel<K, DPMAX>, 256, 0) != hipSuccess) return 1;
-  return b > 0 ? b : 1;
-}
-template <int K>
-int fused_blocks_per_cu_k(int dp) {
-  if (dp <= 16) return fused_blocks_per_cu<K, 16>();
-  if (dp <= 32) return fused_blocks_per_cu<K, 32>();
-  return fused_blocks_per_cu<K, 64>();
-}
-}  // namespace
-
 // Resident fused-kernel blocks per CU for (k, dp) — the host sizes the segment split with it.
 FMLX_API int fmlx_knn_fused_blocks_per_cu(int k, int dp) {
-  if (k <= 4) return fused_blocks_per_cu_k<4>(dp);
-  if (k <= 8) return fused_blocks_per_cu_k<8>(dp);
-  if (k <= 16) return fused_blocks_per_cu_k<16>(dp);
-  if (k <= 32) return fused_blocks_per_cu_k<32>(dp);
-  return fused_blocks_per_cu_k<64>(dp);
+  return with_fused_shape(k, dp, [&](auto K, auto DPMAX) {
+    int b = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, knn_fused_kernel<K.value, DPMAX.value>, 256, 0) != hipSuccess)
+      return 1;
+    return b > 0 ? b : 1;
+  });
 }
 
 FMLX_API int fmlx_knn_fused(const float* Q, long ldq, long nq, int D, const float* Tt, long n, int dp, int k, int S,
@@ -533,11 +517,9 @@ FMLX_API int fmlx_knn_fused(const float* Q, long ldq, long nq, int D, const floa
   if (dp % 4 != 0 || dp > 64 || 2 * dp < D || S < 1 || S > 256) return -1;
   if (S > 1 && (ws_d == nullptr || ws_i == nullptr)) return -1;
   if (nq == 0) return 0;
-  if (k <= 4) return launch_fused_k<4>(Q, ldq, nq, D, Tt, n, dp, k, S, idx, dist, ws_d, ws_i, s);
-  if (k <= 8) return launch_fused_k<8>(Q, ldq, nq, D, Tt, n, dp, k, S, idx, dist, ws_d, ws_i, s);
-  if (k <= 16) return launch_fused_k<16>(Q, ldq, nq, D, Tt, n, dp, k, S, idx, dist, ws_d, ws_i, s);
-  if (k <= 32) return launch_fused_k<32>(Q, ldq, nq, D, Tt, n, dp, k, S, idx, dist, ws_d, ws_i, s);
-  return launch_fused_k<64>(Q, ldq, nq, D, Tt, n, dp, k, S, idx, dist, ws_d, ws_i, s);
+  return with_fused_shape(k, dp, [&](auto K, auto DPMAX) {
+    return launch_fused<K.value, DPMAX.value>(Q, ldq, nq, D, Tt, n, dp, k, S, idx, dist, ws_d, ws_i, s);
+  });
 }
 
 FMLX_DEFINE_PRELOAD()

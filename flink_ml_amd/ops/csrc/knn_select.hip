@@ -217,13 +217,12 @@ FMLX_API int fmlx_knn_select(int acc_f64, const void* G, long ldg, long nq, long
   const size_t es = acc_f64 ? 8 : 4;
   const int cap = kp > 2048 ? kp : 2048;  // LDS entries: the k winners, or the two-pass candidates
   const size_t lds = (size_t)SEL_NB * 4 + (size_t)cap * (es + 4);
-  if (acc_f64)
-    hipLaunchKernelGGL(knn_select_kernel<double>, dim3((unsigned)nq), dim3(SEL_NT), lds, s, (const double*)G, ldg, n,
-                       (const double*)qn, (const double*)tn, k, kp, cap, idx, ldo);
-  else
-    hipLaunchKernelGGL(knn_select_kernel<float>, dim3((unsigned)nq), dim3(SEL_NT), lds, s, (const float*)G, ldg, n,
-                       (const float*)qn, (const float*)tn, k, kp, cap, idx, ldo);
-  return (int)hipGetLastError();
+  return with_acc(acc_f64, [&](auto acc) {
+    typedef decltype(acc) A;
+    hipLaunchKernelGGL(knn_select_kernel<A>, dim3((unsigned)nq), dim3(SEL_NT), lds, s, (const A*)G, ldg, n,
+                       (const A*)qn, (const A*)tn, k, kp, cap, idx, ldo);
+    return (int)hipGetLastError();
+  });
 }
 
 FMLX_DEFINE_PRELOAD()

@@ -158,13 +158,12 @@ FMLX_API int fmlx_ftrl_grad_csr(int acc_f64, const long* indptr, const int* idx,
   hipError_t e = hipMemsetAsync(payload, 0, bytes, s);
   if (e != hipSuccess) return (int)e;
   const int blocks = grid_for(n, 4, 16384);
-  if (acc_f64)
-    hipLaunchKernelGGL(ftrl_grad_csr_kernel<double>, dim3(blocks), dim3(256), 0, s, indptr, idx, (const double*)val,
-                       (const double*)y, (const double*)wt, (const double*)coef, n, d, (double*)payload);
-  else
-    hipLaunchKernelGGL(ftrl_grad_csr_kernel<float>, dim3(blocks), dim3(256), 0, s, indptr, idx, (const float*)val,
-                       (const float*)y, (const float*)wt, (const float*)coef, n, d, (float*)payload);
-  return (int)hipGetLastError();
+  return with_acc(acc_f64, [&](auto acc) {
+    typedef decltype(acc) A;
+    hipLaunchKernelGGL(ftrl_grad_csr_kernel<A>, dim3(blocks), dim3(256), 0, s, indptr, idx, (const A*)val, (const A*)y,
+                       (const A*)wt, (const A*)coef, n, d, (A*)payload);
+    return (int)hipGetLastError();
+  });
 }
 
 // flag: the payload's batch-present slot (null = unconditional); version: int64 device counter
@@ -174,39 +173,35 @@ FMLX_API int fmlx_ftrl_update2(int acc_f64, const void* grad, const void* wsum, 
                                double l1, double l2, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const int blocks = grid_for(d, 256, 2048);
-  if (acc_f64)
-    hipLaunchKernelGGL(ftrl_update_kernel<double>, dim3(blocks), dim3(256), 0, s, (const double*)grad,
-                       (const double*)wsum, wsum_stride, (const double*)flag, world, (double*)coef, (double*)z,
-                       (double*)n, version, d, alpha, beta, l1, l2);
-  else
-    hipLaunchKernelGGL(ftrl_update_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)grad,
-                       (const float*)wsum, wsum_stride, (const float*)flag, world, (float*)coef, (float*)z,
-                       (float*)n, version, d, (float)alpha, (float)beta, (float)l1, (float)l2);
-  return (int)hipGetLastError();
+  return with_acc(acc_f64, [&](auto acc) {
+    typedef decltype(acc) A;
+    hipLaunchKernelGGL(ftrl_update_kernel<A>, dim3(blocks), dim3(256), 0, s, (const A*)grad, (const A*)wsum,
+                       wsum_stride, (const A*)flag, world, (A*)coef, (A*)z, (A*)n, version, d, (A)alpha, (A)beta, (A)l1,
+                       (A)l2);
+    return (int)hipGetLastError();
+  });
 }
 
 FMLX_API int fmlx_okm_local_update(int acc_f64, const void* red, const void* C, const void* W, int k, int D,
                                    double decay_over_p, void* out, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (acc_f64)
-    hipLaunchKernelGGL(okm_local_update_kernel<double>, dim3(k), dim3(256), 0, s, (const double*)red,
-                       (const double*)C, (const double*)W, k, D, decay_over_p, (double*)out);
-  else
-    hipLaunchKernelGGL(okm_local_update_kernel<float>, dim3(k), dim3(256), 0, s, (const float*)red, (const float*)C,
-                       (const float*)W, k, D, (float)decay_over_p, (float*)out);
-  return (int)hipGetLastError();
+  return with_acc(acc_f64, [&](auto acc) {
+    typedef decltype(acc) A;
+    hipLaunchKernelGGL(okm_local_update_kernel<A>, dim3(k), dim3(256), 0, s, (const A*)red, (const A*)C, (const A*)W, k,
+                       D, (A)decay_over_p, (A*)out);
+    return (int)hipGetLastError();
+  });
 }
 
 FMLX_API int fmlx_okm_merge(int acc_f64, const void* m, int k, int D, int world, void* C, void* W, void* Cb, int DP,
                             float* cnorm_bf16, void* cnorm_acc, long* version, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (acc_f64)
-    hipLaunchKernelGGL(okm_merge_kernel<double>, dim3(k), dim3(256), 0, s, (const double*)m, k, D, world, (double*)C,
-                       (double*)W, (bf16_t*)Cb, DP, cnorm_bf16, (double*)cnorm_acc, version);
-  else
-    hipLaunchKernelGGL(okm_merge_kernel<float>, dim3(k), dim3(256), 0, s, (const float*)m, k, D, world, (float*)C,
-                       (float*)W, (bf16_t*)Cb, DP, cnorm_bf16, (float*)cnorm_acc, version);
-  return (int)hipGetLastError();
+  return with_acc(acc_f64, [&](auto acc) {
+    typedef decltype(acc) A;
+    hipLaunchKernelGGL(okm_merge_kernel<A>, dim3(k), dim3(256), 0, s, (const A*)m, k, D, world, (A*)C, (A*)W,
+                       (bf16_t*)Cb, DP, cnorm_bf16, (A*)cnorm_acc, version);
+    return (int)hipGetLastError();
+  });
 }
 
 FMLX_DEFINE_PRELOAD()

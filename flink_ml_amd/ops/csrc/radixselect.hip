@@ -109,18 +109,15 @@ FMLX_API int fmlx_radix_hist(int dtype, const void* X, long ld, long n, int d, c
   if (Q < 1 || Q > kMaxQ || d < 1 || chunks < 1 || (shift & 7)) return -1;
   const long rpc = (n + chunks - 1) / chunks;
   dim3 grid((unsigned)chunks, (unsigned)((d + kCols - 1) / kCols));
-  if (dtype == DT_F32)
-    hipLaunchKernelGGL(radix_hist_kernel<float>, grid, dim3(256), 0, s, (const float*)X, ld, n, d, prefix, Q, shift,
-                       match_all, rpc, part);
-  else if (dtype == DT_F64)
-    hipLaunchKernelGGL(radix_hist_kernel<double>, grid, dim3(256), 0, s, (const double*)X, ld, n, d, prefix, Q,
-                       shift, match_all, rpc, part);
-  else
-    return -1;
   const long rec = (long)Q * d * kBins;
-  hipLaunchKernelGGL(radix_combine_kernel, dim3((unsigned)((rec + 255) / 256)), dim3(256), 0, s, part, chunks, rec,
-                     out);
-  return (int)hipGetLastError();
+  return with_dtype<float, double>(dtype, [&](auto t) {
+    typedef typename decltype(t)::T T;
+    hipLaunchKernelGGL(radix_hist_kernel<T>, grid, dim3(256), 0, s, (const T*)X, ld, n, d, prefix, Q, shift, match_all,
+                       rpc, part);
+    hipLaunchKernelGGL(radix_combine_kernel, dim3((unsigned)((rec + 255) / 256)), dim3(256), 0, s, part, chunks, rec,
+                       out);
+    return (int)hipGetLastError();
+  });
 }
 
 FMLX_DEFINE_PRELOAD()

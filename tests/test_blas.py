@@ -154,6 +154,48 @@ def test_gather_prod_polynomial_terms(dev, dtype):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("tpr", [4, 8, 16, 32, 64])
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32, torch.bfloat16])
+def test_lanes_per_row_variants(dtype, tpr):
+    """Every lanes-per-row variant of the dense row reduction and of the normalizer, called with the
+    width given rather than chosen from d (any width is valid for any d: lanes stride the row)."""
+    _need("cuda")
+    from flink_ml_amd.ops import native
+
+    n, d = 77, 50
+    X = _dense(n, d, tpr, dtype).cuda()
+    Xr = X.double().cpu()
+    acc = torch.float64 if dtype == torch.float64 else torch.float32
+    tol = _tol(dtype) * d
+    out = torch.empty(n, dtype=acc, device="cuda")
+    native.call("fmlx_blas_rowreduce", native.dtype_code(dtype), tpr, native.ptr(X), X.stride(0), None, 0, None, n, d,
+                blas.OP_NORM2, 2.0, native.ptr(out), native.stream_ptr())
+    assert torch.allclose(out.double().cpu(), torch.linalg.vector_norm(Xr, dim=1), rtol=tol, atol=tol)
+    res = torch.empty((n, d), dtype=acc, device="cuda")
+    native.call("fmlx_blas_normalize", native.dtype_code(dtype), tpr, native.ptr(X), X.stride(0), n, d, 2.0, 0,
+                native.ptr(res), res.stride(0), native.stream_ptr())
+    tol = max(_tol(dtype), 1e-6 if dtype == torch.float32 else 0) * 10
+    assert torch.allclose(res.double().cpu(), Xr / torch.linalg.vector_norm(Xr, dim=1)[:, None], rtol=tol, atol=tol)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tpr", [4, 8, 16, 32, 64])
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_csr_lanes_per_row_variants(dtype, tpr):
+    _need("cuda")
+    from flink_ml_amd.ops import native
+
+    X = _csr(90, 300, 70, tpr)
+    Xd = X.to_dense(torch.float64) if dtype == torch.float64 else X.to_dense(torch.float64).float().double()
+    ip, ix, v = X.indptr.cuda(), X.indices.cuda(), X.values.to(dtype).cuda()
+    out = torch.empty(90, dtype=dtype, device="cuda")
+    native.call("fmlx_blas_csr_rowreduce", native.dtype_code(dtype), tpr, native.ptr(ip), native.ptr(ix), native.ptr(v),
+                None, 90, blas.OP_NORM1, 1.0, native.ptr(out), native.stream_ptr())
+    tol = 1e-12 if dtype == torch.float64 else _tol(dtype) * 70
+    assert torch.allclose(out.double().cpu(), Xd.abs().sum(1), rtol=tol, atol=tol)
+
+
+@pytest.mark.gpu
 def test_sync_check_mode_runs_kernels(monkeypatch):
     """FMLX_SYNC_CHECK: every native launch is followed by a device sync (faults are attributed to
     the launching kernel); results are unchanged."""

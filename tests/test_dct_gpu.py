@@ -63,6 +63,40 @@ def test_dct_rows_f64_matches_fp64_product(rows, n, inverse):
     assert bool(((got - ref).abs() <= tol).all()), float((got - ref).abs().max())
 
 
+def _every_k_step(f64, n, inverse):
+    from flink_ml_amd.ops.dct import dct_matrix, dct_rows
+
+    g = torch.Generator().manual_seed(n * 2 + inverse)
+    X = torch.rand((70, n), generator=g, dtype=torch.float64) * 2 - 1
+    M = dct_matrix(n)
+    ref = X @ (M if inverse else M.t())
+    bound = X.abs() @ (M if inverse else M.t()).abs()
+    if f64:
+        got = dct_rows(X.cuda(), inverse).cpu()
+        tol = 1e-15 * bound * n + 1e-16
+    else:
+        got = dct_rows(X.float().cuda(), inverse).double().cpu()
+        tol = 3e-7 * bound + 1e-7
+    assert got.dtype == torch.float64 and bool(((got - ref).abs() <= tol).all()), float((got - ref).abs().max())
+
+
+@pytest.mark.parametrize("inverse", [False, True])
+@pytest.mark.parametrize("ks", range(1, 17))
+def test_dct_rows_every_k_step_count(ks, inverse):
+    """One kernel per number of k steps KP/4 = ⌈⌈n/2⌉/4⌉ = 1 … 16: n = 8·ks takes the 16-byte row
+    path, n = 8·ks − 2 (not a multiple of 4) the scalar one; same bounds as the tests above."""
+    _need_gpu()
+    _every_k_step(False, 8 * ks, inverse)
+    _every_k_step(False, 8 * ks - 2, inverse)
+
+
+@pytest.mark.parametrize("inverse", [False, True])
+@pytest.mark.parametrize("ks", range(1, 17))
+def test_dct_rows_f64_every_k_step_count(ks, inverse):
+    _need_gpu()
+    _every_k_step(True, 8 * ks, inverse)
+
+
 def test_dct_stage_fp64_takes_the_kernel():
     _need_gpu()
     from flink_ml_amd import Table

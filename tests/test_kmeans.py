@@ -164,6 +164,65 @@ def test_gpu_assign_generic(dtype, metric):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("full", [True, False])
+@pytest.mark.parametrize("KS", [1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 16])
+def test_gpu_assign_bf16_every_k_step_count(KS, full):
+    """Each shipped K-step count of the MFMA assign, with rows that fill the padded width (the
+    unguarded loads) and rows six short of it (an even row stride: the MFMA path's condition)."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from flink_ml_amd.ops import kmeans as kk
+
+    D, k = 16 * KS - (0 if full else 6), 10
+    g = torch.Generator().manual_seed(KS * 2 + full)
+    X = torch.randn((300, D), generator=g).to(torch.bfloat16)
+    C = torch.randn((k, D), generator=g, dtype=torch.float64)
+    cb = kk.CentroidBuffers(k, D, torch.device("cuda"), torch.float32)
+    assert cb.KS == KS and kk.mfma_ok(X.cuda(), "euclidean")
+    cb.set(C)
+    lab = kk.assign(X.cuda(), cb, "euclidean").cpu().long()
+    Xf, Cf = X.float(), C.to(torch.bfloat16).float()
+    d = (Cf ** 2).sum(1)[None, :] - 2 * Xf @ Cf.T
+    ref = torch.argmin(d, 1)
+    dsel = d.gather(1, lab[:, None]).squeeze(1)
+    dref = d.gather(1, ref[:, None]).squeeze(1)
+    assert torch.all((lab == ref) | ((dsel - dref).abs() <= 1e-3 * (1 + dref.abs())))
+    assert (lab == ref).float().mean() > 0.99
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("D", [64, 65, 128, 129, 256, 257, 512, 513, 1024, 1025])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32, torch.float64])
+def test_gpu_round_row_width_rungs(dtype, D):
+    """Both sides of every row-width rung of the wave-per-row assign and of the chunk sum (values per
+    lane 1 / 2 / 4 / 8 / 16). Past 1024 the assign takes the thread-per-row kernel and the chunk sum
+    refuses the width (−3)."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from flink_ml_amd.ops import kmeans as kk
+
+    n, k = 240, 5
+    g = torch.Generator().manual_seed(D)
+    C = torch.randn((k, D), generator=g, dtype=torch.float64)
+    X = (C[torch.arange(n) % k] + 0.05 * torch.randn((n, D), generator=g, dtype=torch.float64)).to(dtype)
+    cb = kk.CentroidBuffers(k, D, torch.device("cuda"), torch.float64 if dtype == torch.float64 else torch.float32)
+    cb.set(C)
+    rnd = kk.KMeansRound(X.cuda(), k, "manhattan")  # not the MFMA assign: fmlx_kmeans_assign_generic
+    if D > 1024:
+        with pytest.raises(RuntimeError, match=r"fmlx_kmeans_chunk_sum failed with error -3$"):
+            rnd.run(cb)
+    else:
+        got = rnd.run(cb).cpu().double()
+    lab = rnd.labels.cpu().long()
+    ref = kk.torch_assign(X, C.to(dtype), "manhattan")
+    assert (lab == ref).float().mean() > 0.999
+    if D <= 1024:
+        ref_sums = torch.zeros((k, D), dtype=torch.float64).index_add_(0, lab, X.to(torch.float64))
+        assert torch.allclose(got[: k * D].reshape(k, D), ref_sums, rtol=1e-5, atol=1e-3)
+        assert torch.equal(got[k * D:], torch.bincount(lab, minlength=k).double())
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["stable", "radix", "arrival"])
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32, torch.float64])
 def test_gpu_round_payload_matches_torch(dtype, mode, monkeypatch):

@@ -138,6 +138,39 @@ def test_fused_topk_exact_vs_fp64(d, k):
     torch.testing.assert_close(dist.double().cpu(), rdist, rtol=1e-6, atol=0)
 
 
+@pytest.mark.parametrize("dp", [16, 20, 32, 36, 64])
+@pytest.mark.parametrize("k", [4, 5, 8, 9, 16, 17, 32, 33, 64])
+def test_fused_topk_list_and_width_rungs(k, dp):
+    """Both sides of every rung of the fused kernel's list length (4 / 8 / 16 / 32 / 64) and packed
+    width (16 / 32 / 64); the occupancy query goes through the same (k, dp) map as the launch."""
+    from flink_ml_amd.ops import knn as ko
+    from flink_ml_amd.ops import native
+
+    Q, T = _int_data(70, 200, 2 * dp, seed=k * 67 + dp)
+    pack = ko.TrainPack(T.float().cuda(), (T * T).sum(1).cuda())
+    assert pack.dp == dp
+    assert native.kernels().fmlx_knn_fused_blocks_per_cu(k, dp) >= 1
+    idx, dist = ko.fused_topk(Q.float().cuda(), pack, k, with_dist=True)
+    ridx, rdist = _ref_fp64(Q, T, k)
+    assert torch.equal(idx.long().cpu(), ridx)
+    torch.testing.assert_close(dist.double().cpu(), rdist, rtol=1e-6, atol=0)
+
+
+@pytest.mark.parametrize("k", [1, 2, 3, 4, 5, 8, 9, 16, 17, 32])
+def test_topk_list_length_rungs(k):
+    from flink_ml_amd.ops import knn as ko
+
+    g = torch.Generator(device="cpu").manual_seed(k)
+    Q = torch.randn((70, 24), generator=g).cuda()
+    T = torch.randn((203, 24), generator=g).cuda()
+    G = Q @ T.t()
+    qn, tn = (Q * Q).sum(1), (T * T).sum(1)
+    idx, dist = ko.topk_from_products(G, qn, tn, k, with_dist=True)
+    ridx, rdist = _ref_topk(G, qn, tn, k)
+    torch.testing.assert_close(dist.double().cpu(), rdist, rtol=2e-7, atol=0)
+    assert (idx.long().cpu() == ridx).float().mean() > 0.999
+
+
 @pytest.mark.parametrize("segments", [1, 2, 5, 64])
 @pytest.mark.parametrize("n", [37, 64, 1000, 20011])
 def test_fused_topk_segments_and_tails(segments, n):
