@@ -93,12 +93,19 @@ struct GlmTail {
   long long* trace;  // diagnostics (null = off): per block a record of TRACE_REC stamps in 100 MHz
                      // s_memrealtime ticks (scripts/trace_glm_blocks.py): {start, rows done, end,
                      // hw id, prologue done}, then the loader path's {loader past the prologue,
-                     // prefetched step 0, 1, … seen landed}
+                     // prefetched step 0, 1, … seen landed} and, from TRACE_HEAD on, the links of
+                     // its launch head
 };
 constexpr int ACC_MAX_REPS = 8;
 constexpr int TRACE_REC = 16;       // int64 words per block
 constexpr int TRACE_PROLOGUE = 4;   // consumer wave 0, after the prologue's barrier
 constexpr int TRACE_LOADER = 5;     // loader wave past the prologue's barrier, then one per prefetched step
+// the loader path's launch head, link by link (deferred TAIL_UPDATE): consumer wave 0 knows the
+// round number, has issued the previous round's accumulator loads, has them; the loader wave knows
+// the round number, has issued its first fill
+constexpr int TRACE_HEAD = 11;
+enum { HEAD_ROUND = 0, HEAD_ACC_ISSUED = 1, HEAD_ACC_LANDED = 2, HEAD_LD_ROUND = 3, HEAD_LD_FILL = 4 };
+static_assert(TRACE_HEAD + HEAD_LD_FILL < TRACE_REC, "the head's stamps fit the record");
 
 
 // Replaces this rank's feedback fb[0..stride) (in LDS) by the rank-order sum over all ranks.
@@ -359,10 +366,16 @@ __device__ bool defer_prologue(const GlmTail& tl, A* coef, int* state, int e, in
 // as glm_round_tail_atomic's one_pass form does. d <= 2·NT on this path (rows of at most 128
 // 16-byte chunks), so a thread owns at most two columns. Replicas are summed in defer_prologue's
 // order: the two give bit-identical w_e.
-template <typename A, int NT>
-__device__ bool defer_prologue_consumers(const GlmTail& tl, A* coef, int* state, int e, int d, A* wl, int* stopw) {
+// RT > 0 (the lean head): the replica count is the template value (the launcher passes
+// tl.acc_reps == RT), so the replica loads are straight-line code. issued() runs right behind the
+// loads (the lean head requests its first labels there: loads return in order, so labels requested
+// first would stand between the accumulator and the update). ts (diagnostics, with `trace`):
+// {loads issued, loads landed}; the second stamp waits for vmcnt(0).
+template <typename A, int NT, int RT = 0, typename F>
+__device__ bool defer_prologue_consumers(const GlmTail& tl, A* coef, int* state, int e, int d, A* wl, int* stopw,
+                                         bool trace, long long (&ts)[2], F&& issued) {
   const int tid = threadIdx.x;
-  const int R = tl.acc_reps > 1 ? tl.acc_reps : 1;
+  const int R = RT > 0 ? RT : (tl.acc_reps > 1 ? tl.acc_reps : 1);
   const long ald = tl.acc_ld;
   const long slot = (long)ACC_MAX_REPS * ald;
   A* ring = (A*)tl.acc;
@@ -372,6 +385,7 @@ __device__ bool defer_prologue_consumers(const GlmTail& tl, A* coef, int* state,
   const long ca = tid, cb = tid + NT;
   bool stop = false;
   if (e == 0) {
+    issued();
     if (ca < d) wl[ca] = coef[ca];
     if (cb < d) wl[cb] = coef[cb];
   } else {
@@ -387,6 +401,13 @@ __device__ bool defer_prologue_consumers(const GlmTail& tl, A* coef, int* state,
       vb[q] = q < R ? ld_agent(prev + q * ald + lb) : (A)0;
     }
     const A wa = wp[la], wb = wp[lb];
+    if (trace) {
+      asm volatile("" ::: "memory");
+      ts[0] = (long long)__builtin_amdgcn_s_memrealtime();
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      ts[1] = (long long)__builtin_amdgcn_s_memrealtime();
+    }
+    issued();
     A W = (A)0, L = (A)0, ga = (A)0, gb = (A)0;
 #pragma unroll
     for (int q = 0; q < ACC_MAX_REPS; ++q) {
@@ -592,18 +613,57 @@ constexpr int LOADER = -1;
 #endif
 constexpr int LOADER_SLOTS = FMLX_LOADER_SLOTS;
 constexpr int LOADER_SLOT_BYTES = 16384;  // 8 rows × 2 KiB
-template <typename T, int EPC, int CPL, int U, int WPB, bool NT, int DEPTH = 0>
+//
+// HEAD (loader path only) selects the launch head: 0 = the generic one, which reads every choice
+// from GlmTail; R > 0 = the lean head of the flagship form — deferred TAIL_UPDATE, atomic flat
+// tail, R accumulator replicas, all compile-time — in which nothing stands between the launch and
+// the first row request, or the accumulator loads, that they do not need:
+//   * [ST_DONE] and both round words are read in ONE memory round trip and selected afterwards
+//     (the generic head reads [ST_DONE], returns or not, then reads its round word: two trips);
+//   * the loader wave issues its prefill as soon as the batch's first row is known — the step
+//     count (a 64-bit division) and everything else of the frame come after it;
+//   * the consumers request the accumulator replicas in straight-line code (no branch and no
+//     argument reload per replica) and their first labels behind them, not in front.
+// Row loop, epilogue and atomics are the same text for both heads.
+template <typename T, int EPC, int CPL, int U, int WPB, bool NT, int DEPTH = 0, int HEAD = 0>
 __global__ __launch_bounds__((WPB + (DEPTH < 0 ? 1 : 0)) * 64, (DEPTH < 0 ? 1 : glm_min_waves<T, EPC, CPL, U>())) void glm_round_kernel(
     const T* X, long ld, const typename AccOf<T>::type* y,
     const typename AccOf<T>::type* wt, typename AccOf<T>::type* coef,
     long n, int d, long B, int loss, int* state, typename AccOf<T>::type* partials, GlmTail tl) {
   typedef typename AccOf<T>::type A;
+  // (the lean head's deferred mode is written `LEAN || tl.defer` at each of the flag's uses: read
+  // through a helper, the register-loop instantiations came out with other SGPR spill counts)
+  constexpr bool LEAN = HEAD > 0;
+  static_assert(!LEAN || DEPTH < 0, "the lean head belongs to the loader path");
+  if constexpr (LEAN) {
+    // Every argument the head reads is requested here, ahead of the first wait (the empty asm
+    // statements only pin the values into registers at this point): the arguments span five cache
+    // lines, and fetched where they are used they cost one scalar-cache miss after the other.
+    asm volatile("" ::"s"(state), "s"(tl.parity), "s"(tl.nbatch), "s"(n), "s"(B), "s"(X), "s"(ld), "s"(d),
+                 "s"(gridDim.x), "s"(tl.ring_off), "s"(tl.wl_off), "s"(tl.max_iter));
+    asm volatile("" ::"s"(y), "s"(wt), "s"(coef), "s"(tl.acc), "s"(tl.acc_ld), "s"(tl.cw), "s"(tl.feedback), "s"(tl.acc_reps),
+                 "s"(tl.trace));
+  }
   const long long t_start = tl.trace ? (long long)__builtin_amdgcn_s_memrealtime() : 0;
   int e;
-  if (tl.defer) {
+  if constexpr (LEAN) {
+    // three independent loads, one wait (all three values are pinned before the branch, or the
+    // compiler sinks the round words behind it); launch e publishes into the word it does not read
+    const int done = state[ST_DONE], r0 = state[ST_ROUND], r1 = state[ST_ROUND_ALT];
+    asm volatile("" ::"v"(done), "v"(r0), "v"(r1));
+    if (done) return;
+    e = __builtin_amdgcn_readfirstlane(tl.parity ? r1 : r0);
+  } else if (tl.defer) {
     if (state[ST_DONE]) return;
     e = state[tl.parity ? ST_ROUND_ALT : ST_ROUND];
   } else if (!round_running(state, e)) return;
+  long long t_round = 0;  // diagnostics: the round number is in a register
+  if constexpr (DEPTH < 0) {
+    if (tl.trace) {
+      asm volatile("; round %0" ::"s"(__builtin_amdgcn_readfirstlane(e)) : "memory");
+      t_round = (long long)__builtin_amdgcn_s_memrealtime();
+    }
+  }
   long start = 0, end = 0;  // a rank with no rows (or a zero local batch) still joins the tail
   if (n > 0 && B > 0) {
     // batches per pass: precomputed by the launcher (a 64-bit division per wave otherwise)
@@ -642,7 +702,7 @@ __global__ __launch_bounds__((WPB + (DEPTH < 0 ? 1 : 0)) * 64, (DEPTH < 0 ? 1 : 
   typedef __attribute__((address_space(3))) A lds_acc_t;
   const lds_acc_t* wlds = (const lds_acc_t*)(smem_w + tl.wl_off);
   auto load_w = [&]() {
-    if (tl.defer) {
+    if (LEAN || tl.defer) {
 #pragma unroll
       for (int k = 0; k < CPL; ++k) {
         const int c = lane + 64 * k;
@@ -840,7 +900,11 @@ __global__ __launch_bounds__((WPB + (DEPTH < 0 ? 1 : 0)) * 64, (DEPTH < 0 ? 1 : 
     const unsigned ring_a = __builtin_amdgcn_readfirstlane((unsigned)(size_t)ring);
     const bool loader = wave == WPB;
     const long rb0 = start + (long)blockIdx.x * WPB;          // the block's first row
-    const long nj = rb0 < end ? (end - rb0 + W - 1) / W : 0;  // steps of this block (block-uniform)
+    // steps of this block (block-uniform); the lean head counts them (a 64-bit division) in each
+    // role's own code, behind the requests that do not need the count
+    long nj = 0;
+    auto count_steps = [&]() { nj = rb0 < end ? (end - rb0 + W - 1) / W : 0; };
+    if constexpr (!LEAN) count_steps();
     const bool dense = ld == (long)d;
     const int c1 = lane + 64 < nch ? lane + 64 : nch - 1;
     auto fill = [&](long k) {
@@ -867,16 +931,20 @@ __global__ __launch_bounds__((WPB + (DEPTH < 0 ? 1 : 0)) * 64, (DEPTH < 0 ? 1 : 
     // The two roles share no code from here to the end of the rows: a join between them makes the
     // compiler wait for vmcnt(0) in the loader wave (the consumers' label loads are pending on one
     // side of it), which drains the DMA.
-    const bool xg = tl.mode == TAIL_XGMI;
+    const bool xg = !LEAN && tl.mode == TAIL_XGMI;
     // the block's stop word follows its w image (launch_grad_k sizes it)
     int* stopw = reinterpret_cast<int*>(wdef + d);
-    long long t_pro = 0, t_land[S - 2] = {};
+    long long t_pro = 0, t_land[S - 2] = {}, t_fill = 0, t_acc[2] = {};
     if (loader) {
-      const int pre = tl.defer && xg ? 2 : S - 2;
+      const int pre = (LEAN || tl.defer) && xg ? 2 : S - 2;
 #pragma unroll
-      for (int k = 0; k < S - 2; ++k)
-        if (k < pre && k < nj) fill(k);
-      if (tl.defer) {
+      for (int k = 0; k < S - 2; ++k) {
+        // (lean head: step k exists when its first row lies inside the batch, i.e. k < nj)
+        if (k < pre && (LEAN ? rb0 + k * W < end : k < nj)) fill(k);
+        if (k == 0 && tl.trace) t_fill = (long long)__builtin_amdgcn_s_memrealtime();
+      }
+      if constexpr (LEAN) count_steps();
+      if (LEAN || tl.defer) {
         bool stop;
         if (xg) {
           stop = defer_prologue_xgmi<A>(tl, coef, state, e, d, wdef);
@@ -907,10 +975,22 @@ __global__ __launch_bounds__((WPB + (DEPTH < 0 ? 1 : 0)) * 64, (DEPTH < 0 ? 1 : 
         __builtin_amdgcn_s_barrier();
       }
     } else {
-      if (nj > 0) load_labels(0);
-      if (tl.defer && (xg ? defer_prologue_xgmi<A>(tl, coef, state, e, d, wdef)
-                          : defer_prologue_consumers<A, WPB * 64>(tl, coef, state, e, d, wdef, stopw)))
-        return;
+      const bool ts = tl.trace != nullptr;
+      if constexpr (LEAN) {
+        if (defer_prologue_consumers<A, WPB * 64, HEAD>(tl, coef, state, e, d, wdef, stopw, ts, t_acc, [&]() {
+              // unconditional (the launcher gives this head batches of at least one row, and
+              // load_labels clamps into the batch): behind a branch the waits for the accumulator
+              // would be counted for the path without these two loads, i.e. would wait for them
+              load_labels(0);
+            }))
+          return;
+        count_steps();
+      } else {
+        if (nj > 0) load_labels(0);
+        if (tl.defer && (xg ? defer_prologue_xgmi<A>(tl, coef, state, e, d, wdef)
+                            : defer_prologue_consumers<A, WPB * 64>(tl, coef, state, e, d, wdef, stopw, ts, t_acc, []() {})))
+          return;
+      }
       if (tl.trace && wave == 0) t_pro = (long long)__builtin_amdgcn_s_memrealtime();
       if (nj > 0) {
         load_w();
@@ -943,9 +1023,14 @@ __global__ __launch_bounds__((WPB + (DEPTH < 0 ? 1 : 0)) * 64, (DEPTH < 0 ? 1 : 
       if (loader) {
         tr[TRACE_LOADER] = t_pro;
 #pragma unroll
-        for (int i = 0; i < S - 2; ++i) tr[TRACE_LOADER + 1 + i] = t_land[i];
+        for (int i = 0; i < S - 2 && TRACE_LOADER + 1 + i < TRACE_HEAD; ++i) tr[TRACE_LOADER + 1 + i] = t_land[i];
+        tr[TRACE_HEAD + HEAD_LD_ROUND] = t_round;
+        tr[TRACE_HEAD + HEAD_LD_FILL] = t_fill;
       } else {
         tr[TRACE_PROLOGUE] = t_pro;
+        tr[TRACE_HEAD + HEAD_ROUND] = t_round;
+        tr[TRACE_HEAD + HEAD_ACC_ISSUED] = t_acc[0];
+        tr[TRACE_HEAD + HEAD_ACC_LANDED] = t_acc[1];
       }
     }
   } else {
@@ -968,8 +1053,8 @@ __global__ __launch_bounds__((WPB + (DEPTH < 0 ? 1 : 0)) * 64, (DEPTH < 0 ? 1 : 
     load_rows(r + step, U, r, xb, yb, wb, vb);
   }
   // deferred mode: complete the previous round while the first rows are in flight
-  if (tl.defer && (tl.mode == TAIL_XGMI ? defer_prologue_xgmi<A>(tl, coef, state, e, d, wdef)
-                                        : defer_prologue<A>(tl, coef, state, e, d, wdef)))
+  if ((LEAN || tl.defer) && (tl.mode == TAIL_XGMI ? defer_prologue_xgmi<A>(tl, coef, state, e, d, wdef)
+                                          : defer_prologue<A>(tl, coef, state, e, d, wdef)))
     return;
   if (nst > 0) {
     load_w();
@@ -1027,7 +1112,7 @@ __global__ __launch_bounds__((WPB + (DEPTH < 0 ? 1 : 0)) * 64, (DEPTH < 0 ? 1 : 
 
   extern __shared__ __align__(16) unsigned char smem_raw[];
   A* buf = reinterpret_cast<A*>(smem_raw);          // [WPB][d] (flat) or [WPB/2][d] (tree)
-  const bool flat = tl.mode != TAIL_PARTIALS && !tl.det && tl.flat_lds;
+  const bool flat = LEAN || (tl.mode != TAIL_PARTIALS && !tl.det && tl.flat_lds);
   A* lw = buf + (flat ? WPB : WPB / 2) * (long)d;   // [WPB][2]
   int* sflag = reinterpret_cast<int*>(lw + WPB * 2);
   const bool worker = DEPTH >= 0 || wave < WPB;  // the loader wave holds no sums
@@ -1048,7 +1133,7 @@ __global__ __launch_bounds__((WPB + (DEPTH < 0 ? 1 : 0)) * 64, (DEPTH < 0 ? 1 : 
     // replica b mod acc_reps: at most ceil(nb / reps) adders per address (float atomics keep
     // their full rate up to ~32 adders per address; 256 on one 4 KB row serialise)
     const int rep = (int)(blockIdx.x % (tl.acc_reps > 1 ? tl.acc_reps : 1));
-    A* gacc = (A*)tl.acc + (long)rep * tl.acc_ld + (tl.defer ? (long)(e % 3) * ACC_MAX_REPS * tl.acc_ld : 0L);
+    A* gacc = (A*)tl.acc + (long)rep * tl.acc_ld + (LEAN || tl.defer ? (long)(e % 3) * ACC_MAX_REPS * tl.acc_ld : 0L);
     const long stride = d + 2;
     for (long c = threadIdx.x; c < stride; c += blockDim.x) {
       A v = (A)0;
@@ -1066,7 +1151,7 @@ __global__ __launch_bounds__((WPB + (DEPTH < 0 ? 1 : 0)) * 64, (DEPTH < 0 ? 1 : 
       __syncthreads();
       if (threadIdx.x == 0) tl.trace[(long)blockIdx.x * TRACE_REC + 2] = (long long)__builtin_amdgcn_s_memrealtime();
     }
-    if (tl.defer) return;  // launch e + 1 completes this round
+    if (LEAN || tl.defer) return;  // launch e + 1 completes this round
     glm_round_tail_atomic<A>(tl, d, coef, state, e, buf, sflag);
     return;
   }
@@ -1447,6 +1532,9 @@ static long long* g_trace = nullptr;  // per-block timestamps of the next launch
 // register loads), 0 = 16-byte register loads
 static int g_row_select = -1;
 static int g_row_path = 0;  // row path of the last fused-round launch (−1 loader, 0 registers)
+// launch head of the loader path's flagship form (glm_round_kernel, HEAD): 1 = lean, 0 = generic
+static int g_head = 1;
+static int g_last_head = 0;  // HEAD of the last loader-path launch (0 generic, else its replica count)
 
 // what every layer of the fused round's dispatch passes on unchanged
 struct RoundArgs {
@@ -1499,6 +1587,19 @@ int launch_grad_k(const RoundArgs& a, GlmTail t2, bool nt, hipStream_t s) {
     return (int)hipGetLastError();
   };
   if constexpr (EPC * sizeof(T) == 16 && sizeof(T) == 2) {
+    if constexpr (PATH == LOADER) {
+      // the lean head: deferred TAIL_UPDATE on the atomic flat tail with 1, 2, 4 or 8 replicas
+      // (launch_grad_u has checked the rest of what `defer` needs) and a batch of at least one row;
+      // every other form, and any other replica count, takes the generic head
+      if (nt && g_head && t2.defer && t2.mode == TAIL_UPDATE && !t2.det && t2.flat_lds && a.n > 0 && a.B > 0) {
+        const int rc = with_value<1, 2, 4, 8>(t2.acc_reps > 1 ? t2.acc_reps : 1, [&](auto r) {
+          g_last_head = r.value;
+          return launch(glm_round_kernel<T, EPC, CPL, U, WPB, true, PATH, r.value>);
+        }, -100);
+        if (rc != -100) return rc;
+      }
+      g_last_head = 0;
+    }
     if (nt) return launch(glm_round_kernel<T, EPC, CPL, U, WPB, true, PATH>);
   }
   if constexpr (PATH == 0) return launch(glm_round_kernel<T, EPC, CPL, U, WPB, false>);
@@ -1528,8 +1629,12 @@ int launch_grad_u(const RoundArgs& a, const GlmTail& tl, int flags, hipStream_t 
     }
   }
 #endif
+#ifdef FMLX_ISA_PROBE_LOADER  // the loader instantiations only (ISA inspection)
+  return -9;
+#else
   g_row_path = 0;
   return launch_grad_k<T, EPC, CPL, U, 0>(a, t2, nt, s);
+#endif
 }
 
 // rows in flight per wave = 2·U (software pipeline); u == 0 picks the default for the shape
@@ -1544,12 +1649,16 @@ int launch_grad(int u, const RoundArgs& a, const GlmTail& tl, int flags, hipStre
 #ifdef FMLX_ISA_PROBE_U  // one row-loop variant only (ISA inspection)
   return launch_grad_u<T, EPC, CPL, FMLX_ISA_PROBE_U>(a, tl, flags, s);
 #endif
+#ifdef FMLX_ISA_PROBE_LOADER
+  return launch_grad_u<T, EPC, CPL, 1>(a, tl, flags, s);
+#else
   // (compile-time guard: the multi-row variants of wide rows would only exist to spill)
   if constexpr (BYTES <= 32) {
     if (u >= 4) return launch_grad_u<T, EPC, CPL, 4>(a, tl, flags, s);
     if (u >= 2) return launch_grad_u<T, EPC, CPL, 2>(a, tl, flags, s);
   }
   return launch_grad_u<T, EPC, CPL, 1>(a, tl, flags, s);
+#endif
 }
 
 #ifndef FMLX_ISA_PROBE
@@ -1639,6 +1748,17 @@ FMLX_API int fmlx_glm_set_dma(int path) {
   g_row_select = path;
   return 0;
 }
+
+// Launch head of the loader path's flagship form: 1 = lean (default), 0 = generic (tests and A/B
+// runs compare the two in one build)
+FMLX_API int fmlx_glm_set_head(int head) {
+  if (head != 0 && head != 1) return -1;
+  g_head = head;
+  return 0;
+}
+
+// which head the last loader-path launch took: 0 generic, R > 0 lean with R replicas (tests)
+FMLX_API int fmlx_glm_last_head() { return g_last_head; }
 
 // which row path the last fused-round launch of this process took (tests, A/B scripts)
 FMLX_API int fmlx_glm_row_path() { return g_row_path; }

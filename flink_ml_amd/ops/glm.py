@@ -95,6 +95,24 @@ def set_dma(path: int) -> None:
                          "streamed batches) or 0 (register loads), not %r" % (path,))
 
 
+# Launch head of the loader/consumer path's flagship form (deferred TAIL_UPDATE, atomic tail, 1, 2,
+# 4 or 8 accumulator replicas; csrc/glm.hip glm_round_kernel, HEAD): 1 = lean (default), 0 = generic.
+# bench.py 2.62–2.66 -> 2.69–2.77 G samples/s, kernel A/B 36.0–36.9 -> 34.1–35.6 us per round against
+# the build without it; the two heads in one build 36.4 vs 35.3 (profiles/r16/INDEX.md)
+HEAD = 1
+
+
+def set_head(head: int) -> None:
+    """Launch head of the loader/consumer path (A/B and test knob): 1 = lean, 0 = generic."""
+    if native.kernels().fmlx_glm_set_head(int(head)) != 0:
+        raise ValueError("launch head (set_head) must be 1 (lean) or 0 (generic), not %r" % (head,))
+
+
+def last_head() -> int:
+    """Head of the last loader/consumer launch: 0 generic, R > 0 the lean head for R replicas."""
+    return int(native.kernels().fmlx_glm_last_head())
+
+
 def row_path() -> int:
     """Row path the last fused-round launch took: -1 loader/consumer, 0 register loads."""
     return int(native.kernels().fmlx_glm_row_path())
@@ -104,7 +122,9 @@ def set_trace(buf: Optional[torch.Tensor]) -> None:
     """Diagnostics: fused-round launches write per-block {start, rows done, atomics drained, hw
     id, prologue done, loader past the prologue, prefetched step 0, 1, … landed} s_memrealtime
     stamps (100 MHz) into ``buf`` (int64 [blocks, 16], csrc/glm.hip TRACE_REC; the sparse rounds
-    keep their own [blocks, 4] record); None switches off."""
+    keep their own [blocks, 4] record); None switches off. The loader/consumer path adds, from word
+    11 (TRACE_HEAD), the links of its launch head: {round number known, accumulator loads issued,
+    landed} of consumer wave 0 and {round number known, first fill issued} of the loader wave."""
     native.kernels().fmlx_glm_set_trace(native.ptr(buf))
 
 

@@ -6,11 +6,14 @@ block start, plus per-XCD means; then the three spans of a block (start → prol
 done → end) as per-block medians and spreads. On the loader/consumer row path the loader wave also
 stamps when it got past the prologue and when it saw each prefetched ring step landed (it drains
 its prefetch for that, so a traced round starts its ring a little later than an untraced one):
-"steps landed" counts the prefetched steps that were in LDS when the prologue ended.
+"steps landed" counts the prefetched steps that were in LDS when the prologue ended. The same path
+stamps the links of its launch head (the "head" spans): consumer wave 0 knows the round number, has
+issued the previous round's accumulator loads, has them; the loader wave knows the round number and
+has issued its first fill. --head 1 | 0 picks the lean or the generic head.
 
 Shows how much of a round is launch skew, prologue, load imbalance (the slowest block's rows) and
 tail.
-Usage: python scripts/trace_glm_blocks.py [--rounds 20] [--defer 1]
+Usage: python scripts/trace_glm_blocks.py [--rounds 20] [--defer 1] [--head 1]
 """
 import argparse
 import json
@@ -29,6 +32,8 @@ from flink_ml_amd.ops import glm as gk  # noqa: E402
 TICK_US = 0.01  # s_memrealtime runs at 100 MHz
 REC = 16  # int64 words per block (csrc/glm.hip TRACE_REC)
 PROLOGUE, LOADER = 4, 5  # (TRACE_PROLOGUE, TRACE_LOADER: loader past the prologue, then one per prefetched step)
+HEAD = 11  # TRACE_HEAD: round known, accumulator loads issued, landed (consumer wave 0); round known, first fill (loader)
+H_ROUND, H_ISSUED, H_LANDED, H_LD_ROUND, H_LD_FILL = range(HEAD, HEAD + 5)
 # a prefetched step counts as landed at the end of the prologue when the loader's wait for it
 # returned within this many ticks of the previous stamp (one s_memrealtime read takes 3–6)
 LANDED_TICKS = 10
@@ -41,9 +46,11 @@ def main():
     ap.add_argument("--batch", type=int, default=100_000)
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--defer", type=int, default=1)
+    ap.add_argument("--head", type=int, default=gk.HEAD, help="launch head of the loader path: 1 lean, 0 generic")
     a = ap.parse_args()
     dev = torch.device("cuda")
     gk.DEFER = bool(a.defer)
+    gk.set_head(a.head)
     g = torch.Generator(device=dev).manual_seed(1)
     X = torch.empty((a.rows, a.dim), dtype=torch.bfloat16, device=dev)
     for s in range(0, a.rows, 1 << 20):
@@ -96,6 +103,7 @@ def main():
                       "block_done_spread_us_if_per_block_mean_removed": round(float(
                           np.median(np.ptp(done - done.mean(0, keepdims=True), axis=1)) * TICK_US), 2)}))
     spans(rows)
+    print(json.dumps({"head": gk.last_head() if gk.row_path() == -1 else None}))
     keys = ["start_max_us", "rows_done_min_us", "rows_done_med_us", "rows_done_max_us", "block_rows_us_med"]
     xm = {x: round(statistics.median(s["rows_done_mean_by_xcd"][x] for s in summary), 2)
           for x in summary[0]["rows_done_mean_by_xcd"]}
@@ -118,7 +126,17 @@ def spans(rows):
     if (t[:, :, PROLOGUE] > 0).all():
         out["start_to_prologue_done_us"] = stat(t[:, :, PROLOGUE] - t[:, :, 0])
         out["prologue_done_to_rows_done_us"] = stat(t[:, :, 1] - t[:, :, PROLOGUE])
-        ld = t[:, :, LOADER:]
+        if (t[:, :, H_ROUND] > 0).all() and (t[:, :, H_ISSUED] > 0).all():  # (launch 0 has no accumulator to read)
+            out["head_consumer_us"] = {
+                "start_to_round_known": stat(t[:, :, H_ROUND] - t[:, :, 0]),
+                "round_known_to_acc_issued": stat(t[:, :, H_ISSUED] - t[:, :, H_ROUND]),
+                "acc_issued_to_landed": stat(t[:, :, H_LANDED] - t[:, :, H_ISSUED]),
+                "acc_landed_to_prologue_done": stat(t[:, :, PROLOGUE] - t[:, :, H_LANDED])}
+            out["head_loader_us"] = {
+                "start_to_round_known": stat(t[:, :, H_LD_ROUND] - t[:, :, 0]),
+                "round_known_to_first_fill": stat(t[:, :, H_LD_FILL] - t[:, :, H_LD_ROUND]),
+                "start_to_first_fill": stat(t[:, :, H_LD_FILL] - t[:, :, 0])}
+        ld = t[:, :, LOADER:HEAD]
         ns = int((ld[0, 0] > 0).sum()) - 1  # prefetched steps
         if ns > 0:
             d = np.diff(ld[:, :, :ns + 1], axis=2)  # wait for step i, from the previous stamp
