@@ -4,7 +4,9 @@ maxabsscaler,robustscaler,variancethresholdselector}``).
 fit = one fused column-statistics pass over the rank's HBM-resident partition (``colstats.hip``,
 K15) + one all-reduce of the fixed-size statistics; transform = one fused per-column affine
 kernel (``affine_cols``, K16). Sparse inputs stay sparse where the reference keeps them sparse
-(MaxAbsScaler, StandardScaler without centering).
+(MaxAbsScaler, StandardScaler without centering), and the fits of StandardScaler, MinMaxScaler and
+VarianceThresholdSelector reduce a sparse column over its CSR arrays (``colstats_csr.hip``,
+``FMLX_COLSTATS_CSR``) instead of densifying it.
 """
 from __future__ import annotations
 
@@ -26,6 +28,14 @@ from .common import (all_reduce_stats, dec_dense, dense_input, dense_vec, enc_de
 
 
 def _stats(table: Table, col: str) -> dict:
+    if fo.COLSTATS_CSR_ROUTE != "0" and table.is_sparse(col):
+        # a sparse column (CSR, or a list of SparseVectors) the rule routes: per-column sums over its
+        # column-major copy (colstats_csr.hip), no n x d matrix
+        X = vector_input(table, col)
+        if fo.csr_stats_route(X, X.values.device):
+            s = fo.column_stats_csr(X)
+            s.pop("stored")  # (rank-local; the fits do not use it)
+            return all_reduce_stats(s)
     X = dense_input(table, col)
     return all_reduce_stats(fo.column_stats(X))
 

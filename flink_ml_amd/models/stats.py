@@ -12,6 +12,9 @@ one all-reduce combines them:
   Pearson statistic, dof = (V-1)(L-1), p-value and statistic rounded HALF_UP to 11
   decimals like ``ChiSqTest.java:440-455``.
 
+ANOVATest and FValueTest reduce a sparse feature column over its CSR arrays (``colstats_csr.hip``,
+``FMLX_COLSTATS_CSR``) instead of densifying it; ChiSqTest densifies.
+
 Distribution CDFs come from scipy (commons-math3 in the reference).
 """
 from __future__ import annotations
@@ -51,6 +54,29 @@ def features_and_labels(t: Table, features_col: str, label_col: str,
         raise ValueError("Input data must contain label value.")
     y = t.scalars(label_col, dtype=torch.float64, device=X.device)
     return X, y
+
+
+def sparse_features_and_labels(t: Table, features_col: str, label_col: str):
+    """``(SparseColumn, labels)`` on the compute device when the feature column is sparse (CSR, or a
+    list of SparseVectors) and its statistics take the CSR route (``ops.features.csr_stats_route``),
+    else None: the caller densifies through ``features_and_labels``. fp32 / fp64 values are kept as
+    stored (the kernel accumulates in fp64 itself)."""
+    if fo.COLSTATS_CSR_ROUTE == "0" or not t.is_sparse(features_col):
+        return None
+    dev = config.compute_device()
+    c = t.column(features_col)
+    if isinstance(c, SparseColumn):
+        if not fo.csr_stats_route(c, dev):
+            return None
+        X = c.to(device=dev, dtype=None if c.values.dtype in (torch.float32, torch.float64) else torch.float64)
+    else:
+        X = config.features_for_compute(t, features_col, allow_sparse=True, exact=True)
+        if not fo.csr_stats_route(X, dev):
+            return None
+    lab = t.column(label_col)
+    if isinstance(lab, list) and any(v is None for v in lab):
+        raise ValueError("Input data must contain label value.")
+    return X, t.scalars(label_col, dtype=torch.float64, device=dev)
 
 
 def global_sorted_unique(v: torch.Tensor) -> torch.Tensor:
@@ -136,11 +162,14 @@ class ANOVATest(AlgoOperator, _TestParams):
     JAVA_CLASS_NAME = "org.apache.flink.ml.stats.anovatest.ANOVATest"
 
     def compute(self, t: Table):
-        X, y = features_and_labels(t, self.get(self.FEATURES_COL), self.get(self.LABEL_COL), keep_dtype=True)
+        sp = sparse_features_and_labels(t, self.get(self.FEATURES_COL), self.get(self.LABEL_COL))
+        X, y = sp or features_and_labels(t, self.get(self.FEATURES_COL), self.get(self.LABEL_COL), keep_dtype=True)
         cls = global_sorted_unique(y)
-        C, d = cls.numel(), X.shape[1]
+        C, d = cls.numel(), X.size if sp else X.shape[1]
         ci = torch.searchsorted(cls, y)
-        if C <= fo.MAX_GROUPS:
+        if sp:  # per-class sums over the column-major copy (colstats_csr.hip), a window of 32 classes a pass
+            S, tot, totsq = fo.group_colstats_csr(X, ci, C)
+        elif C <= fo.MAX_GROUPS:
             S, tot, totsq = fo.group_colstats(X, ci, C)
         else:
             Xd = X.to(torch.float64)
@@ -182,15 +211,16 @@ class FValueTest(AlgoOperator, _TestParams):
     JAVA_CLASS_NAME = "org.apache.flink.ml.stats.fvaluetest.FValueTest"
 
     def compute(self, t: Table):
-        X, y = features_and_labels(t, self.get(self.FEATURES_COL), self.get(self.LABEL_COL), keep_dtype=True)
-        d = X.shape[1]
+        sp = sparse_features_and_labels(t, self.get(self.FEATURES_COL), self.get(self.LABEL_COL))
+        X, y = sp or features_and_labels(t, self.get(self.FEATURES_COL), self.get(self.LABEL_COL), keep_dtype=True)
+        d = X.size if sp else X.shape[1]
         ym = _reduce(torch.stack([torch.tensor(float(y.numel()), dtype=torch.float64, device=y.device), y.sum(),
                                   (y * y).sum()]))
         n = float(ym[0])
         my = ym[1] / n
         sy = torch.sqrt((ym[2] / n - my * my) * n / (n - 1))
         yc = y - my
-        S, sx_, sxx = fo.group_colstats(X, None, 1, yc)
+        S, sx_, sxx = fo.group_colstats_csr(X, None, 1, yc) if sp else fo.group_colstats(X, None, 1, yc)
         mom = _reduce(torch.cat([S[0], yc.sum()[None], sx_, sxx]))
         mx = mom[d + 1:2 * d + 1] / n
         sx = torch.sqrt((mom[2 * d + 1:] / n - mx * mx) * n / (n - 1))

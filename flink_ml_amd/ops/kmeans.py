@@ -13,6 +13,8 @@ import numpy as np
 import torch
 
 from . import native
+from .csr import ColumnMajor
+from .csr import csr_arrays as _csr_arrays
 
 # rows grouped by cluster with the hand-written STABLE counting sort (csrc/groupsort.hip
 # st_*: per-tile histograms, column scan, ordered scatter — rows of a cluster stay in row order,
@@ -411,11 +413,6 @@ def csr_features(table, col: str, k: int):
     return config.features_for_compute(table, col, allow_sparse=True)
 
 
-def _csr_arrays(X, dtype):
-    return (X.indptr.to(torch.int64).contiguous(), X.indices.to(torch.int32).contiguous(),
-            X.values.to(dtype).contiguous())
-
-
 class SparseCentroidBuffers:
     """The centroid image of the CSR kernels: centroid-minor ``Ct[D][kp]`` (padding lanes 0), the
     per-centroid norms ``[‖c‖ | ‖c‖² | ‖c‖₁]`` and the weights. ``cent`` is its [k, D] view."""
@@ -481,50 +478,20 @@ class SparseKMeansRound:
     column-major copy (built here, once per fit) → ``payload`` = ``[D·kp sums | k counts]``."""
 
     def __init__(self, X, k: int, metric: str):
-        from . import glm as _glm
-
         dev = X.values.device
         self.n, self.D, self.k, self.metric = len(X), X.size, int(k), metric
         self.kp = csr_kp(self.k)
-        self.acc = torch.float64 if X.values.dtype == torch.float64 else torch.float32
-        self.indptr, self.idx, self.val = _csr_arrays(X, self.acc)
+        # the column-major copy (ops/csr.py): built once per fit, a column's entries in row order
+        cm = self.cm = ColumnMajor(X, int(CSR_COL_SEGMENT))
+        self.acc, self.nnz, self.seg, self.err = cm.acc, cm.nnz, cm.seg, cm.err
+        self.indptr, self.idx, self.val = cm.indptr, cm.idx, cm.val
         self.X = type(X)(self.indptr, self.idx, self.val, self.D)
-        self.nnz = nnz = int(self.idx.numel())
-        self.seg = int(CSR_COL_SEGMENT)
+        self.colptr, self.crow, self.cval = cm.colptr, cm.crow, cm.cval
+        self.nlong, self.long_col, self.long_seg0 = cm.nlong, cm.long_col, cm.long_seg0
+        self.nsegs, self.seg_col, self.seg_k = cm.nsegs, cm.seg_col, cm.seg_k
         self.labels = torch.empty(self.n, dtype=torch.int32, device=dev)
         self.payload = torch.zeros(self.D * self.kp + self.k, dtype=self.acc, device=dev)
         self.counts = torch.zeros(self.k, dtype=torch.int32, device=dev)  # re-zeroed by every round
-        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.colptr = torch.zeros(self.D + 1, dtype=torch.int64, device=dev)
-        self.crow = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
-        self.cval = torch.empty(max(nnz, 1), dtype=self.acc, device=dev)
-        stream = native.stream_ptr(dev)
-        if nnz:
-            # (column, entry id) through the stable segmented radix sort: one segment, ceil(log2 D)
-            # key bits; a column's entries stay in row order
-            bits = max(1, int(self.D - 1).bit_length())
-            keys = torch.empty(nnz, dtype=torch.int32, device=dev)
-            ids = torch.empty(nnz, dtype=torch.int32, device=dev)
-            erow = torch.empty(nnz, dtype=torch.int32, device=dev)
-            native.call("fmlx_kmeans_csr_prepare", native.ptr(self.indptr), native.ptr(self.idx), self.n, self.D,
-                        native.ptr(keys), native.ptr(ids), native.ptr(erow), native.ptr(self.err), stream)
-            keys, ids = _glm.seg_sort(keys, ids, [0, nnz], [0], bits)
-            native.call("fmlx_kmeans_csr_colptr", native.ptr(keys), nnz, self.D, native.ptr(self.colptr), stream)
-            native.call("fmlx_kmeans_csr_gather", int(self.acc == torch.float64), native.ptr(ids), native.ptr(erow),
-                        native.ptr(self.val), nnz, native.ptr(self.crow), native.ptr(self.cval), stream)
-            del keys, ids, erow  # the sort scratch goes with them
-        # columns longer than a segment: (column, first segment) and the per-segment table
-        lens = self.colptr[1:] - self.colptr[:-1]
-        long_col = torch.nonzero(lens > self.seg).reshape(-1)
-        self.nlong = int(long_col.numel())
-        nseg = (lens[long_col] + self.seg - 1) // self.seg
-        self.long_seg0 = torch.zeros(self.nlong + 1, dtype=torch.int64, device=dev)
-        self.long_seg0[1:] = torch.cumsum(nseg, 0)
-        self.nsegs = int(self.long_seg0[-1].item())
-        self.long_col = long_col.to(torch.int32)
-        self.seg_col = torch.repeat_interleave(self.long_col, nseg, output_size=self.nsegs)
-        self.seg_k = (torch.arange(self.nsegs, device=dev)
-                      - torch.repeat_interleave(self.long_seg0[:-1], nseg, output_size=self.nsegs)).to(torch.int32)
         self.partial = torch.zeros(max(self.nsegs, 1) * self.kp, dtype=self.acc, device=dev)
 
     def run(self, cb: SparseCentroidBuffers) -> torch.Tensor:
