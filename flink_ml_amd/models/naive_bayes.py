@@ -11,6 +11,16 @@ the tables of all columns are all-reduced in one call. Then, as in ``GenerateMod
 predict: every feature value becomes a column index into one flattened [L, ΣV_j] log-probability
 table, so a block of rows is a single gather + sum over features; argmax with the reference's
 first-max rule. An unseen feature value raises (the reference fails with an NPE).
+
+A sparse feature column (``SparseColumn``, or a list of SparseVectors) under the route of
+``ops.catstats.catstats_csr_route`` (``FMLX_COLSTATS_CSR``) is neither densified by fit nor by
+predict. fit takes the counts of the stored entries (``catstats.value_label_counts_csr``) and applies
+the same expressions to the same integers: the model data is byte-identical to the dense route's.
+predict scores a row as ``base[l] + Σ over its stored entries (T[l, j, v] − T[l, j, 0])`` with
+``base[l] = pi[l] + Σ_j T[l, j, 0]`` (``csrc/catstats_csr.hip`` nb_csr_predict: a wave per row, a lane
+per label); a feature without a value 0 in the model is unseen as soon as one row does not store
+it. A model with a non-finite theta (smoothing 0: log 0) keeps the dense route: a difference of
+infinities has no delta form.
 """
 from __future__ import annotations
 
@@ -25,6 +35,7 @@ from ..common.param import HasFeaturesCol, HasLabelCol, HasPredictionCol
 from ..io import read_write as rw
 from ..io import serialization as ser
 from ..linalg.vectors import DenseVector
+from ..ops import features as fo
 from ..param.param import FloatParam, ParamValidators, StringParam
 from ..parallel import comm
 from ..table import SparseColumn, Table
@@ -32,7 +43,8 @@ from ..utils.java import java_double_hash, java_hashmap_order
 from .base import ModelWithData
 from .feature.common import get_world_distributed
 from .linear import rw_update
-from .stats import features_and_labels, global_sorted_unique, value_label_counts
+from .stats import (features_and_labels, global_sorted_unique, sparse_categorical_features_and_labels,
+                    value_label_counts)
 
 
 class NaiveBayesModelParams(HasFeaturesCol, HasPredictionCol):
@@ -92,10 +104,75 @@ class NaiveBayesModel(ModelWithData, NaiveBayesModelParams):
                 torch.as_tensor(np.asarray(pi.values), device=dev), torch.as_tensor(np.asarray(labels.values),
                                                                                    device=dev))
 
+    def _csr_state(self):
+        """The model as the CSR predict reads it: the features' value lists in one array with their
+        offsets, where the value 0 sits in each (-1: the model has none), the label-minor image of
+        the log-probabilities relative to the value 0, and the value-0 log-probabilities [L, nf].
+        None for a model with a non-finite theta."""
+        st = getattr(self, "_csr_cache", None)
+        if st is not None and st[0] is self._md_cache:
+            return st[1]
+        vals, offs, table, pi, labels = self._model_state()
+        res = None
+        if bool(torch.isfinite(table).all()) and table.shape[1] < 2 ** 31:
+            dev = table.device
+            nf = len(vals)
+            Vn = torch.tensor([v.numel() for v in vals], dtype=torch.int64, device=dev)
+            off = torch.zeros(nf + 1, dtype=torch.int64, device=dev)
+            off[1:] = torch.cumsum(Vn, 0)
+            vflat = torch.cat(vals) if nf else torch.zeros(0, dtype=torch.float64, device=dev)
+            zero_at = torch.nonzero(vflat == 0.0).reshape(-1)
+            zpos = torch.full((nf,), -1, dtype=torch.int64, device=dev)
+            zcol = torch.searchsorted(off, zero_at, right=True) - 1
+            zpos[zcol] = zero_at
+            zrow = torch.zeros((table.shape[0], nf), dtype=torch.float64, device=dev)
+            zrow[:, zcol] = table[:, zero_at]
+            delta = (table - torch.repeat_interleave(zrow, Vn, dim=1, output_size=int(vflat.numel()))).t().contiguous()
+            res = (off, vflat, zpos, delta, zrow)
+        self._csr_cache = (self._md_cache, res)
+        return res
+
+    def _transform_csr(self, t: Table, X: SparseColumn):
+        """Predictions for a sparse column from its stored entries; None for a model that keeps the
+        dense route."""
+        st = self._csr_state()
+        if st is None:
+            return None
+        from ..ops import catstats
+
+        off, vflat, zpos, delta, zrow = st
+        _, _, table, pi, labels = self._model_state()
+        n, d = len(X), X.size
+        if d > zpos.numel():
+            raise ValueError("The input vector has %d features, the model has %d." % (d, zpos.numel()))
+        X = X.to(device=table.device)
+        base = pi + zrow[:, :d].sum(dim=1)
+        idx, unseen = catstats.nb_csr_predict(X, off, vflat, delta, base)
+        nozero = torch.nonzero(zpos[:d] < 0).reshape(-1)
+        if nozero.numel() and n:
+            # a feature without a value 0 in the model: unseen as soon as one row does not store it
+            stored = torch.bincount(X.indices.to(torch.int64), minlength=d)[:d]
+            short = nozero[stored[nozero] < n]
+            if short.numel():
+                unseen = min(unseen, int(short[0]))
+        if unseen < d:
+            raise RuntimeError("Feature %d of the input contains a value unseen in training." % unseen)
+        return [t.with_column(self.get(self.PREDICTION_COL), labels[idx.to(torch.int64)].to(torch.float64))]
+
     def transform(self, *inputs):
         t = inputs[0]
         vals, offs, table, pi, labels = self._model_state()
         c = t.column(self.get(self.FEATURES_COL))
+        if fo.COLSTATS_CSR_ROUTE != "0" and t.is_sparse(self.get(self.FEATURES_COL)):
+            from ..ops import catstats
+
+            Xs = c if isinstance(c, SparseColumn) else config.features_for_compute(
+                t, self.get(self.FEATURES_COL), allow_sparse=True, exact=True)
+            if catstats.catstats_csr_route(Xs, table.device):
+                out = self._transform_csr(t, Xs)
+                if out is not None:
+                    return out
+            c = Xs
         X = c.to_dense(torch.float64, device=table.device) if isinstance(c, SparseColumn) else \
             config.features_for_compute(t, self.get(self.FEATURES_COL), allow_sparse=False).to(table.device,
                                                                                                 torch.float64)
@@ -212,6 +289,23 @@ def _label_value_counts_device(X: torch.Tensor, li: torch.Tensor, L: int, dist: 
     return counts.astype(np.float64), vals, slots, n_lab.cpu().numpy()
 
 
+def _label_value_counts_csr(X: SparseColumn, li: torch.Tensor, L: int, dist: bool):
+    """``_label_value_counts`` from the ragged table of a sparse column's stored entries
+    (``catstats.value_label_counts_csr``; across ranks the merge of the ranks' tables): per-feature
+    sorted distinct values, ``cell(j, l)`` = the counts of feature j's values under label index l,
+    and the rows per label (fp64, the same integers as the dense route's). None when the table is
+    too large: the caller densifies."""
+    from ..ops import catstats
+
+    rc = catstats.global_value_label_counts_csr(X, li, L) if dist else catstats.value_label_counts_csr(X, li, L)
+    if rc is None:
+        return None
+    colfirst, values, counts, n_l = rc.numpy()
+    counts = counts.astype(np.float64)
+    vals = [values[colfirst[j]:colfirst[j + 1]] for j in range(X.size)]
+    return vals, (lambda j, l: counts[colfirst[j]:colfirst[j + 1], l]), n_l.astype(np.float64)
+
+
 def _labels_integral(y: torch.Tensor) -> bool:
     """No label with a fractional part (NaN counts as one, ±inf does not: y != round(y)). On the
     GPU one library reduction answers it for finite labels (torch's compare / round / any kernels
@@ -237,20 +331,29 @@ class NaiveBayes(Estimator, NaiveBayesParams):
         if isinstance(fc, list) and len({v.size() for v in fc}) > 1:
             raise ValueError("Feature vectors should be of equal length.")
         # on the GPU the stored dtype stays (the contingency kernels read f32 or f64 themselves)
-        X, y = features_and_labels(t, self.get(self.FEATURES_COL), self.get(self.LABEL_COL), keep_dtype=True)
+        sp = sparse_categorical_features_and_labels(t, self.get(self.FEATURES_COL), self.get(self.LABEL_COL))
+        X, y = sp or features_and_labels(t, self.get(self.FEATURES_COL), self.get(self.LABEL_COL), keep_dtype=True)
         if not _labels_integral(y):
             raise ValueError("Label value should be indexed number.")
         s = self.get(self.SMOOTHING)
         dist = get_world_distributed()
+        d = X.size if sp else X.shape[1]
         if dist:
             try:
-                comm.check_equal_across_ranks(int(X.shape[1]), "feature vector length")
+                comm.check_equal_across_ranks(int(d), "feature vector length")
             except ValueError:
                 raise ValueError("Feature vectors should be of equal length.") from None
         labels = global_sorted_unique(y)
-        L, d = labels.numel(), X.shape[1]
+        L = labels.numel()
         li = torch.searchsorted(labels, y)  # binary search per row
-        counts, vals, slots, n_l = _label_value_counts(X, li, L, dist)
+        ragged = _label_value_counts_csr(X, li, L, dist) if sp else None
+        if ragged is not None:
+            vals, cell, n_l = ragged
+        else:
+            if sp:  # (the table of distinct values is too large for the CSR route)
+                X = features_and_labels(t, self.get(self.FEATURES_COL), self.get(self.LABEL_COL), keep_dtype=True)[0]
+            counts, vals, slots, n_l = _label_value_counts(X, li, L, dist)
+            cell = lambda j, l: counts[j, l, slots[j]]  # noqa: E731
         labels_np = labels.cpu().numpy()
         # the reference's model lists labels in HashMap<Double, _> order
         order = [int(np.searchsorted(labels_np, v)) for v in java_hashmap_order(labels_np.tolist(), java_double_hash)]
@@ -261,7 +364,7 @@ class NaiveBayes(Estimator, NaiveBayesParams):
             row = []
             for j in range(d):
                 V = vals[j].size
-                logs = np.log(counts[j, li_, slots[j]] + s) - np.log(n_l[li_] + s * V)
+                logs = np.log(cell(j, li_) + s) - np.log(n_l[li_] + s * V)
                 row.append(dict(zip(vals[j].tolist(), logs.tolist())))
             theta.append(row)
         pi = DenseVector(np.array([np.log(n_l[i] * d + s) - pi_log for i in order]))

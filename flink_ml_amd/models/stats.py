@@ -13,7 +13,11 @@ one all-reduce combines them:
   decimals like ``ChiSqTest.java:440-455``.
 
 ANOVATest and FValueTest reduce a sparse feature column over its CSR arrays (``colstats_csr.hip``,
-``FMLX_COLSTATS_CSR``) instead of densifying it; ChiSqTest densifies.
+``FMLX_COLSTATS_CSR``) instead of densifying it; ChiSqTest counts one from its stored entries
+(``catstats_csr.hip``, the same knob; ``ops.catstats.value_label_counts_csr``) and densifies only
+when the table of distinct values would pass ``catstats.MAX_TABLE`` cells. Its statistics are
+evaluated for all features at once (``chisq_statistics``), bit for bit the per-feature expression,
+so the route never changes a p-value.
 
 Distribution CDFs come from scipy (commons-math3 in the reference).
 """
@@ -56,22 +60,24 @@ def features_and_labels(t: Table, features_col: str, label_col: str,
     return X, y
 
 
-def sparse_features_and_labels(t: Table, features_col: str, label_col: str):
+def sparse_features_and_labels(t: Table, features_col: str, label_col: str, route=None):
     """``(SparseColumn, labels)`` on the compute device when the feature column is sparse (CSR, or a
-    list of SparseVectors) and its statistics take the CSR route (``ops.features.csr_stats_route``),
+    list of SparseVectors) and its statistics take the CSR route (``route``: by default
+    ``ops.features.csr_stats_route``; ``ops.catstats.catstats_csr_route`` for contingency counts),
     else None: the caller densifies through ``features_and_labels``. fp32 / fp64 values are kept as
     stored (the kernel accumulates in fp64 itself)."""
     if fo.COLSTATS_CSR_ROUTE == "0" or not t.is_sparse(features_col):
         return None
+    route = route or fo.csr_stats_route
     dev = config.compute_device()
     c = t.column(features_col)
     if isinstance(c, SparseColumn):
-        if not fo.csr_stats_route(c, dev):
+        if not route(c, dev):
             return None
         X = c.to(device=dev, dtype=None if c.values.dtype in (torch.float32, torch.float64) else torch.float64)
     else:
         X = config.features_for_compute(t, features_col, allow_sparse=True, exact=True)
-        if not fo.csr_stats_route(X, dev):
+        if not route(X, dev):
             return None
     lab = t.column(label_col)
     if isinstance(lab, list) and any(v is None for v in lab):
@@ -245,11 +251,97 @@ def _round11(v: float) -> float:
     return float(Decimal(v).quantize(Decimal("1e-11"), rounding=ROUND_HALF_UP))
 
 
+def sparse_categorical_features_and_labels(t: Table, features_col: str, label_col: str):
+    """``sparse_features_and_labels`` under the contingency counts' route. Across ranks the CSR and
+    the dense route run different collectives, so the ranks take the CSR route only if all do."""
+    from ..ops import catstats
+
+    sp = sparse_features_and_labels(t, features_col, label_col, catstats.catstats_csr_route)
+    if get_world_distributed() and fo.COLSTATS_CSR_ROUTE != "0" and t.is_sparse(features_col):
+        no = torch.tensor([0.0 if sp else 1.0], dtype=torch.float64, device=config.compute_device())
+        if float(comm.all_reduce(no, "max")[0]) != 0.0:
+            return None
+    return sp
+
+
+def chisq_statistic_one(obs: np.ndarray) -> float:
+    """Pearson statistic of one [V, L] table of observed counts."""
+    n = obs.sum()
+    exp = np.outer(obs.sum(1), obs.sum(0)) / n
+    return float(((obs - exp) ** 2 / exp).sum())
+
+
+CHISQ_BATCH_CELLS = 1 << 22  # cells of one batched evaluation (rows are independent: any split gives the same bits)
+
+
+def chisq_statistics(Vn: np.ndarray, flat: np.ndarray, L: int) -> np.ndarray:
+    """``chisq_statistic_one`` of every feature at once: feature j's [V_j, L] block (value-major) lies
+    at offset Σ_{i<j} V_i·L of ``flat``. Features are grouped by V and a group is one array
+    expression; the counts are integers, so every sum but the last is exact in any order, and the
+    last runs along the contiguous V·L cells of a table like the per-table sum (bit-identical;
+    tests/test_catstats_csr.py pins it). dof = 0 gives 0."""
+    Vn = np.asarray(Vn, dtype=np.int64)
+    off = np.concatenate([[0], np.cumsum(Vn * L)])
+    stat = np.zeros(Vn.shape[0], dtype=np.float64)
+    if L < 2:
+        return stat
+    for V in np.unique(Vn[Vn > 1]).tolist():
+        js_all = np.nonzero(Vn == V)[0]
+        cells = np.arange(V * L)
+        step = max(1, CHISQ_BATCH_CELLS // (V * L))
+        for s in range(0, js_all.shape[0], step):
+            js = js_all[s:s + step]
+            obs = flat[off[js][:, None] + cells[None, :]].reshape(-1, V, L)
+            n = obs.sum(axis=(1, 2))
+            exp = obs.sum(axis=2)[:, :, None] * obs.sum(axis=1)[:, None, :] / n[:, None, None]
+            stat[js] = ((obs - exp) ** 2 / exp).reshape(js.shape[0], V * L).sum(axis=1)
+    return stat
+
+
+def chisq_finish(Vn, flat: np.ndarray, L: int):
+    """(p-values, degrees of freedom, statistics) of all features, rounded like the reference."""
+    Vn = np.asarray(Vn, dtype=np.int64)
+    dof = (Vn - 1) * (L - 1)
+    live = dof > 0
+    stat = np.where(live, chisq_statistics(Vn, np.asarray(flat, dtype=np.float64), L), 0.0)
+    p = np.ones(Vn.shape[0], dtype=np.float64)
+    if live.any():
+        p[live] = 1.0 - sps.chi2.cdf(stat[live], dof[live])
+    memo = {}
+
+    def rnd(v):
+        r = memo.get(v)
+        if r is None:
+            r = memo[v] = _round11(v)
+        return r
+
+    return [rnd(v) for v in p.tolist()], dof.tolist(), [rnd(v) for v in stat.tolist()]
+
+
 @rw.register_stage
 class ChiSqTest(AlgoOperator, _TestParams):
     JAVA_CLASS_NAME = "org.apache.flink.ml.stats.chisqtest.ChiSqTest"
 
+    def _compute_csr(self, X: SparseColumn, y: torch.Tensor):
+        """The test on a sparse column's stored entries; None when the table is too large."""
+        from ..ops import catstats
+
+        labels = global_sorted_unique(y)
+        L = labels.numel()
+        li = torch.searchsorted(labels, y)
+        rc = catstats.global_value_label_counts_csr(X, li, L) if get_world_distributed() else \
+            catstats.value_label_counts_csr(X, li, L)
+        if rc is None:
+            return None
+        colfirst, _, counts, _ = rc.numpy()
+        return chisq_finish(np.diff(colfirst), counts.reshape(-1), L)
+
     def compute(self, t: Table):
+        sp = sparse_categorical_features_and_labels(t, self.get(self.FEATURES_COL), self.get(self.LABEL_COL))
+        if sp:
+            res = self._compute_csr(*sp)
+            if res is not None:
+                return res
         X, y = features_and_labels(t, self.get(self.FEATURES_COL), self.get(self.LABEL_COL), keep_dtype=True)
         labels = global_sorted_unique(y)
         L, d = labels.numel(), X.shape[1]
@@ -276,23 +368,7 @@ class ChiSqTest(AlgoOperator, _TestParams):
                 vi = torch.searchsorted(vals[j], X[:, j].contiguous())
                 tables.append(torch.bincount(vi * L + li, minlength=vals[j].numel() * L).to(torch.float64))
             flat = torch.cat(tables).cpu().numpy() if tables else np.zeros(0)
-        p_out, dof_out, stat_out, off = [], [], [], 0
-        for j in range(d):
-            V = vals[j].numel()
-            obs = flat[off:off + V * L].reshape(V, L)
-            off += V * L
-            n = obs.sum()
-            exp = np.outer(obs.sum(1), obs.sum(0)) / n
-            stat = float(((obs - exp) ** 2 / exp).sum())
-            dof = (V - 1) * (L - 1)
-            if dof == 0:
-                stat, p = 0.0, 1.0
-            else:
-                p = 1.0 - float(sps.chi2.cdf(stat, dof))
-            p_out.append(_round11(p))
-            dof_out.append(dof)
-            stat_out.append(_round11(stat))
-        return p_out, dof_out, stat_out
+        return chisq_finish([v.numel() for v in vals], flat, L)
 
     def transform(self, *inputs):
         p, dof, s = self.compute(inputs[0])

@@ -6,6 +6,12 @@ case) are counted straight into an LDS-privatised table; anything else goes thro
 
 All functions take CUDA tensors; the CPU reference of every result is the torch code in
 ``models/stats.py`` / ``models/naive_bayes.py``.
+
+A CSR feature column (``SparseColumn``) is counted from its stored entries alone
+(``csrc/catstats_csr.hip``, ``value_label_counts_csr``): one radix sort of (column, value) keys, a
+run scan, an integer count per run and label, and the zero row of every column from the label
+totals. The result is a ragged table (``RaggedCounts``) instead of [d, L, Vmax]; the same functions
+run on CPU tensors through a numpy formulation over the CSR arrays (``torch_value_label_counts_csr``).
 """
 from __future__ import annotations
 
@@ -284,3 +290,380 @@ def global_value_label_counts(X: torch.Tensor, li: torch.Tensor, L: int):
             T[j][:, pos] = c_loc[j][:, slots_loc[j]]
     T = comm.all_reduce_sum(torch.from_numpy(T).to(dev)).cpu().numpy()
     return T, union, [np.arange(len(u)) for u in union]
+
+
+# ------------------------------------------------------------------------------------------------
+# CSR feature columns (csrc/catstats_csr.hip): the same counts without an n x D matrix
+# ------------------------------------------------------------------------------------------------
+# The route is under FMLX_COLSTATS_CSR (ops/features.py): "0" densifies, "1" always takes it, "auto"
+# takes it when the densified matrix would exceed the HBM budget or the density nnz / (n·D) is at
+# most CATSTATS_CSR_CROSSOVER. The dense contingency route fills an fp64 n x D matrix and counts
+# every cell, so the column statistics' constant does not transfer: this one is the highest density
+# of a sweep of its own (100,000 rows, D = 1,024 and 16,384, densities 0.1 / 1 / 5 / 20 %;
+# scripts/bench_catstats_sparse.py, profiles/r18/INDEX.md) at which the CSR route won in both run
+# orders at both widths, for the tables alone and for ChiSqTest.compute. It won at every measured
+# density, so the constant is the sweep's highest one; nothing above 20 % was measured.
+CATSTATS_CSR_CROSSOVER = 0.2
+
+
+class RaggedCounts:
+    """Contingency tables of all features as one ragged table: feature j's sorted distinct values are
+    ``values[colfirst[j]:colfirst[j + 1]]`` (fp64; −0 folded into +0, NaN last) and ``counts[u, l]``
+    the rows of label index l that hold value u; ``n_label[l]`` the rows per label. ``paths``: the
+    count kernel's tiles that went through LDS / global atomics; ``err``: the CSR error word."""
+
+    __slots__ = ("colfirst", "values", "counts", "n_label", "paths", "err")
+
+    def __init__(self, colfirst, values, counts, n_label, paths=None, err=None):
+        self.colfirst, self.values, self.counts, self.n_label = colfirst, values, counts, n_label
+        self.paths, self.err = paths, err
+
+    def numpy(self):
+        """(colfirst int64 [D + 1], values fp64 [U], counts int64 [U, L], n_label int64 [L]) on the host."""
+        return (self.colfirst.cpu().numpy().astype(np.int64), self.values.cpu().numpy(),
+                self.counts.cpu().numpy().astype(np.int64), self.n_label.cpu().numpy().astype(np.int64))
+
+
+class StoredCounts:
+    """The stored entries' part of a table, before the zero rows: distinct (column, value) pairs in
+    sorted order, ``ucol[U]`` (int32), ``uval[U]`` (fp64), ``cnt[U, L]``."""
+
+    __slots__ = ("ucol", "uval", "cnt", "paths", "err")
+
+    def __init__(self, ucol, uval, cnt, paths=None, err=None):
+        self.ucol, self.uval, self.cnt, self.paths, self.err = ucol, uval, cnt, paths, err
+
+
+def catstats_csr_route(X, device) -> bool:
+    """Whether the contingency counts of a ``SparseColumn`` take the CSR path."""
+    from . import features as fo
+    from ..table import SparseColumn
+
+    if fo.COLSTATS_CSR_ROUTE == "0" or not isinstance(X, SparseColumn):
+        return False
+    n, D, nnz = len(X), X.size, int(X.indices.numel())
+    if n >= 2 ** 31 or nnz >= 2 ** 31 - 1 or D >= 2 ** 31 or D < 1:
+        return False
+    if fo.COLSTATS_CSR_ROUTE == "1":
+        return True
+    device = torch.device(device)
+    if device.type == "cuda":
+        from .. import config
+        from ..common.outofcore import hbm_budget
+
+        budget = hbm_budget(device)
+        if budget is not None and n * D * torch.empty(0, dtype=config.compute_dtype()).element_size() > budget:
+            return True
+    return nnz <= CATSTATS_CSR_CROSSOVER * n * D
+
+
+def _np_stored(col: np.ndarray, val: np.ndarray, L: int, lab: np.ndarray = None, W: np.ndarray = None):
+    """Distinct (column, value) pairs of entries in sorted order and their counts per label: one per
+    entry at its label index ``lab``, or the entry's row of ``W`` [m, L]."""
+    v = val.astype(np.float64) + 0.0  # −0 → +0
+    order = np.lexsort((v, col))      # (NaN sorts last)
+    c, v = col[order], v[order]
+    m = c.shape[0]
+    head = np.ones(m, dtype=bool)
+    head[1:] = (c[1:] != c[:-1]) | ~((v[1:] == v[:-1]) | (np.isnan(v[1:]) & np.isnan(v[:-1])))
+    gid = np.cumsum(head) - 1
+    U = int(gid[-1]) + 1 if m else 0
+    if W is None:
+        cnt = np.bincount(gid * L + lab[order], minlength=U * L).reshape(U, L).astype(np.int64)
+    else:
+        cnt = np.zeros((U, L), dtype=np.int64)
+        np.add.at(cnt, gid, W[order])
+    return c[head].astype(np.int32), v[head], cnt
+
+
+def _np_zero_merge(ucol, uval, cnt, D: int, n_label: np.ndarray):
+    """The final table of stored counts: per column the zero row n_label − Σ of its other rows, added
+    to a stored zero's row, inserted at its sorted place when any row does not store the column."""
+    L = n_label.shape[0]
+    stored = np.zeros(D, dtype=np.int64)
+    np.add.at(stored, ucol, cnt.sum(1))
+    has_zero = np.zeros(D, dtype=bool)
+    has_zero[ucol[uval == 0.0]] = True
+    ins = np.nonzero(~has_zero & (stored < int(n_label.sum())))[0].astype(np.int32)
+    col = np.concatenate([ucol, ins])
+    val = np.concatenate([uval, np.zeros(ins.shape[0])])
+    out = np.concatenate([cnt, np.zeros((ins.shape[0], L), dtype=np.int64)])
+    order = np.lexsort((val, col))
+    col, val, out = col[order], val[order], out[order]
+    colfirst = np.searchsorted(col, np.arange(D + 1)).astype(np.int64)
+    z = np.nonzero(val == 0.0)[0]
+    others = out.copy()
+    others[z] = 0
+    run = np.concatenate([np.zeros((1, L), dtype=np.int64), np.cumsum(others, 0)])
+    jz = col[z]
+    out[z] = n_label[None, :] - (run[colfirst[jz + 1]] - run[colfirst[jz]])
+    return colfirst, val, out
+
+
+def _np_entries(X, li, L: int):
+    """(column, value, label index) of the entries of a host ``SparseColumn``; raises for a column
+    outside [0, size); entries of rows without a label index in [0, L) are dropped."""
+    n = len(X)
+    col = X.indices.cpu().numpy().astype(np.int64)
+    if col.size and (col.min() < 0 or col.max() >= X.size):
+        raise ValueError("sparse feature index out of range [0, size)")
+    ptr = X.indptr.cpu().numpy().astype(np.int64)
+    lab = np.repeat(np.asarray(li.cpu().numpy(), dtype=np.int64), ptr[1:] - ptr[:-1]) if n else np.zeros(0, np.int64)
+    val = X.values.cpu().numpy()
+    ok = (lab >= 0) & (lab < L)
+    return col[ok], val[ok], lab[ok]
+
+
+def _ragged_from_np(colfirst, val, out, n_label, device="cpu", paths=None, err=None) -> RaggedCounts:
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+    return RaggedCounts(t(colfirst), t(val), t(out), t(n_label), paths, err)
+
+
+def torch_value_label_counts_csr(X, li: torch.Tensor, L: int) -> RaggedCounts:
+    """``value_label_counts_csr`` from the CSR arrays alone on the host (numpy, no n x D array): the
+    CPU path of the route and the oracle of the kernels. Raises for an index outside [0, size)."""
+    col, val, lab = _np_entries(X, li, L)
+    n_label = np.bincount(np.asarray(li.cpu().numpy(), dtype=np.int64), minlength=L)[:L].astype(np.int64)
+    ucol, uval, cnt = _np_stored(col, val, L, lab)
+    return _ragged_from_np(*_np_zero_merge(ucol, uval, cnt, X.size, n_label), n_label)
+
+
+def _value_ranks(val: torch.Tensor):
+    """(vid uint32-in-int32 [m], gval fp64): every fp64 value's rank among the distinct values (one
+    sort of the 64-bit value keys; the value 0 is always one of them) and the values by rank."""
+    dev, m = val.device, int(val.numel())
+    keys = torch.empty(m + 1, dtype=torch.int64, device=dev)
+    pay = torch.empty(m + 1, dtype=torch.int32, device=dev)
+    orand = torch.tensor([0, -1], dtype=torch.int64, device=dev)
+    stream = native.stream_ptr(dev)
+    native.call("fmlx_ccsr_vkeys", native.ptr(val), m, native.ptr(keys), native.ptr(pay), native.ptr(orand), stream)
+    lo, hi = sorting.bit_range(orand)
+    keys, pay = sorting.sort_u64(keys, pay, [0, m + 1], lo, hi)
+    tile = int(native.kernels().fmlx_ccsr_tile())
+    tcnt = torch.empty(-(-(m + 1) // tile) + 1, dtype=torch.int64, device=dev)
+    vid = torch.empty(max(1, m), dtype=torch.int32, device=dev)
+    gval = torch.empty(m + 1, dtype=torch.float64, device=dev)
+    native.call("fmlx_ccsr_vids", native.ptr(keys), native.ptr(pay), m, native.ptr(tcnt), native.ptr(vid),
+                native.ptr(gval), stream)
+    return vid, gval
+
+
+def _count_runs(keys, pay, orand, total: int, L: int, W, gval, err) -> Optional[StoredCounts]:
+    """Sort (column, k32) keys, scan their runs and count per run and label. None when the table
+    would pass MAX_TABLE cells."""
+    dev = keys.device
+    stream = native.stream_ptr(dev)
+    lo, hi = sorting.bit_range(orand)
+    keys, pay = sorting.sort_u64(keys, pay, [0, total], lo, hi)
+    tile = int(native.kernels().fmlx_ccsr_tile())
+    nt = -(-total // tile)
+    tcnt = torch.empty(nt + 1, dtype=torch.int64, device=dev)
+    native.call("fmlx_ccsr_runs", native.ptr(keys), total, native.ptr(tcnt), stream)
+    U = int(tcnt[nt].item())
+    if U * L > MAX_TABLE:
+        return None
+    cnt = torch.zeros((U, L), dtype=torch.int32, device=dev)
+    ucol = torch.empty(U, dtype=torch.int32, device=dev)
+    uval = torch.empty(U, dtype=torch.float64, device=dev)
+    paths = torch.zeros(2, dtype=torch.int32, device=dev)
+    if U:
+        native.call("fmlx_ccsr_count", native.ptr(keys), native.ptr(pay), total, native.ptr(tcnt), L, native.ptr(W),
+                    native.ptr(gval), native.ptr(cnt), native.ptr(ucol), native.ptr(uval), native.ptr(paths), stream)
+    return StoredCounts(ucol, uval, cnt, paths, err)
+
+
+def _empty_stored(L: int, dev) -> StoredCounts:
+    return StoredCounts(torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float64, device=dev),
+                        torch.zeros((0, L), dtype=torch.int32, device=dev), torch.zeros(2, dtype=torch.int32, device=dev),
+                        torch.zeros(1, dtype=torch.int32, device=dev))
+
+
+def stored_counts_csr(X, li: torch.Tensor, L: int) -> Optional[StoredCounts]:
+    """Counts per (column, stored value, label index) of a ``SparseColumn`` on its device, before the
+    zero rows. An index outside [0, size) is skipped and sets ``err`` (``ops.kmeans.check_csr_error``)
+    on the GPU and raises on the CPU. None when the table would pass MAX_TABLE cells."""
+    dev = X.values.device
+    n, D, nnz = len(X), X.size, int(X.indices.numel())
+    if dev.type != "cuda":
+        col, val, lab = _np_entries(X, li, L)
+        ucol, uval, cnt = _np_stored(col, val, L, lab)
+        if cnt.size > MAX_TABLE:
+            return None
+        return StoredCounts(torch.from_numpy(ucol), torch.from_numpy(uval), torch.from_numpy(cnt))
+    if nnz == 0 or n == 0:
+        return _empty_stored(L, dev)
+    indptr = X.indptr.to(torch.int64).contiguous()
+    idx = X.indices.to(torch.int32).contiguous()
+    li = li.to(device=dev, dtype=torch.int32).contiguous()
+    if X.values.dtype == torch.float32:
+        val, vid, gval = X.values.contiguous(), None, None
+    else:
+        val = None
+        vid, gval = _value_ranks(X.values.to(torch.float64).contiguous())
+    keys = torch.empty(nnz, dtype=torch.int64, device=dev)
+    pay = torch.empty(nnz, dtype=torch.int32, device=dev)
+    orand = torch.tensor([0, -1], dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    native.call("fmlx_ccsr_keys", native.ptr(indptr), native.ptr(idx), native.ptr(val), native.ptr(vid), native.ptr(li),
+                n, D, L, native.ptr(keys), native.ptr(pay), native.ptr(orand), native.ptr(err), native.stream_ptr(dev))
+    return _count_runs(keys, pay, orand, nnz, L, None, gval, err)
+
+
+def merge_stored_counts(col: torch.Tensor, val: torch.Tensor, W: torch.Tensor, D: int) -> Optional[StoredCounts]:
+    """One table of several: rows (col[m], val[m], W[m, L]) with repeated (column, value) pairs summed
+    by the same sort + run pass, the rows' counts as weights."""
+    dev, m, L = val.device, int(val.numel()), int(W.shape[1])
+    if dev.type != "cuda":
+        ucol, uval, cnt = _np_stored(col.numpy().astype(np.int64), val.numpy(), L, W=W.numpy().astype(np.int64))
+        return StoredCounts(torch.from_numpy(ucol), torch.from_numpy(uval), torch.from_numpy(cnt))
+    if m == 0:
+        return _empty_stored(L, dev)
+    vid, gval = _value_ranks(val.to(torch.float64).contiguous())
+    keys = torch.empty(m, dtype=torch.int64, device=dev)
+    pay = torch.empty(m, dtype=torch.int32, device=dev)
+    orand = torch.tensor([0, -1], dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    native.call("fmlx_ccsr_ekeys", native.ptr(col.to(torch.int32).contiguous()), native.ptr(vid), m, D, native.ptr(keys),
+                native.ptr(pay), native.ptr(orand), native.ptr(err), native.stream_ptr(dev))
+    return _count_runs(keys, pay, orand, m, L, W.to(torch.int32).contiguous(), gval, err)
+
+
+def zero_merge(st: StoredCounts, D: int, n_label: torch.Tensor) -> Optional[RaggedCounts]:
+    """The final ragged table of stored counts and the label totals (int64 [L]). None when it would
+    pass MAX_TABLE cells."""
+    dev = st.uval.device
+    L = int(n_label.numel())
+    if dev.type != "cuda":
+        out = _np_zero_merge(st.ucol.numpy(), st.uval.numpy(), st.cnt.numpy().astype(np.int64), D,
+                             n_label.numpy().astype(np.int64))
+        return None if out[2].size > MAX_TABLE else _ragged_from_np(*out, n_label.numpy().astype(np.int64))
+    U = int(st.uval.numel())
+    stream = native.stream_ptr(dev)
+    n_label = n_label.to(device=dev, dtype=torch.int64).contiguous()
+    gf = torch.empty(D + 1, dtype=torch.int64, device=dev)
+    flag = torch.empty(D, dtype=torch.int32, device=dev)
+    zr = torch.empty(D, dtype=torch.int32, device=dev)
+    colfirst = torch.empty(D + 1, dtype=torch.int64, device=dev)
+    native.call("fmlx_ccsr_columns", native.ptr(st.ucol), native.ptr(st.uval), native.ptr(st.cnt), U, D, L,
+                int(n_label.sum().item()), native.ptr(gf), native.ptr(flag), native.ptr(zr), native.ptr(colfirst), stream)
+    Uo = int(colfirst[D].item())
+    if Uo * L > MAX_TABLE:
+        return None
+    values = torch.empty(Uo, dtype=torch.float64, device=dev)
+    out = torch.empty((Uo, L), dtype=torch.int32, device=dev)
+    native.call("fmlx_ccsr_merge", native.ptr(st.ucol), native.ptr(st.uval), native.ptr(st.cnt), U, D, L, native.ptr(gf),
+                native.ptr(flag), native.ptr(zr), native.ptr(colfirst), native.ptr(n_label), native.ptr(values),
+                native.ptr(out), stream)
+    return RaggedCounts(colfirst, values, out, n_label, st.paths, st.err)
+
+
+def _n_label(li: torch.Tensor, L: int) -> torch.Tensor:
+    if li.is_cuda:
+        return label_counts(li, L) if li.numel() else torch.zeros(L, dtype=torch.int64, device=li.device)
+    return torch.bincount(li.to(torch.int64), minlength=L)[:L]
+
+
+def value_label_counts_csr(X, li: torch.Tensor, L: int, check: bool = True) -> Optional[RaggedCounts]:
+    """(feature, distinct value, label) counts of a ``SparseColumn`` on its device as a ragged table,
+    the rows that store nothing in a column counting as the value 0. Exact (integer counts). None
+    when the table would pass MAX_TABLE cells: the caller densifies. ``check``: raise for an index
+    outside [0, size) (else the entry is skipped and ``err`` set)."""
+    if X.values.device.type != "cuda":
+        return torch_value_label_counts_csr(X, li, L)
+    st = stored_counts_csr(X, li, L)
+    res = zero_merge(st, X.size, _n_label(li.to(X.values.device), L)) if st is not None else None
+    if check and st is not None:
+        from .kmeans import check_csr_error
+
+        check_csr_error(st)
+    return res
+
+
+def global_value_label_counts_csr(X, li: torch.Tensor, L: int) -> Optional[RaggedCounts]:
+    """``value_label_counts_csr`` over ALL ranks: every rank's stored-entry table and label totals,
+    the tables all-gathered (padded to the longest) and merged by the same sort + run pass with the
+    counts as weights, then the zero rows from the all-reduced label totals. No keyed shuffle, no
+    library sort; every rank ends with the same table."""
+    from ..parallel import comm
+
+    dev = X.values.device
+    li = li.to(dev)
+    st = stored_counts_csr(X, li, L)
+    # (too large a table or a bad index on one rank: every rank learns it before the next collective)
+    bad = 1.0 if st is not None and st.err is not None and int(st.err.item()) else 0.0
+    over = comm.all_reduce(torch.tensor([0.0 if st is not None else 1.0, bad], dtype=torch.float64, device=dev), "max")
+    if float(over[1]) != 0.0:
+        raise ValueError("sparse feature index out of range [0, size)")
+    if float(over[0]) != 0.0:
+        return None
+    n_label = comm.all_reduce_sum(_n_label(li, L).to(torch.float64)).to(torch.int64)
+    U = int(st.uval.numel())
+    M = max(1, int(comm.all_reduce(torch.tensor([float(U)], dtype=torch.float64, device=dev), "max")[0]))
+    blk = torch.zeros((M + 1, L + 2), dtype=torch.float64, device=dev)  # (col, value, counts); last row: U
+    blk[:U, 0] = st.ucol.to(torch.float64)
+    blk[:U, 1] = st.uval
+    blk[:U, 2:] = st.cnt.to(torch.float64)
+    blk[M, 0] = U
+    G = [g.to(dev) for g in comm.all_gather_tensor(blk)]
+    rows = torch.cat([g[:int(g[M, 0].item())] for g in G])
+    merged = merge_stored_counts(rows[:, 0].to(torch.int32), rows[:, 1].contiguous(), rows[:, 2:].to(torch.int64), X.size)
+    return zero_merge(merged, X.size, n_label) if merged is not None else None
+
+
+# ------------------------------------------------------------------------------------------------
+# NaiveBayes prediction on a CSR column (csrc/catstats_csr.hip nb_csr_predict)
+# ------------------------------------------------------------------------------------------------
+NB_NONE = 2 ** 31 - 1  # "no unseen value"
+
+
+def torch_nb_csr_predict(X, off: torch.Tensor, vflat: torch.Tensor, delta: torch.Tensor, base: torch.Tensor):
+    """``nb_csr_predict`` in torch over the CSR arrays alone (the CPU path): a vectorised binary
+    search of every entry's value in its feature's value list, the deltas added in stored-entry
+    order (``index_add_`` on the host), first maximum."""
+    n, D = len(X), X.size
+    idx = X.indices.to(torch.int64)
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= D):
+        raise ValueError("sparse feature index out of range [0, size)")
+    v = X.values.to(torch.float64)
+    lo, hi = off[idx].clone(), off[idx + 1].clone()
+    end = hi.clone()
+    top = max(int(vflat.numel()) - 1, 0)
+    vpad = vflat if vflat.numel() else torch.zeros(1, dtype=torch.float64, device=vflat.device)
+    while bool((lo < hi).any()):
+        act = lo < hi
+        mid = (lo + hi) // 2
+        less = vpad[mid.clamp(max=top)] < v
+        lo = torch.where(act & less, mid + 1, lo)
+        hi = torch.where(act & ~less, mid, hi)
+    found = (lo < end) & (vpad[lo.clamp(max=top)] == v)
+    unseen = int(idx[~found].min()) if bool((~found).any()) else NB_NONE
+    ptr = X.indptr.to(torch.int64)
+    rows = torch.repeat_interleave(torch.arange(n, device=v.device), ptr[1:] - ptr[:-1], output_size=int(idx.numel()))
+    score = base[None, :].repeat(n, 1)
+    score.index_add_(0, rows[found], delta[lo[found]])
+    return torch.argmax(score, dim=1).to(torch.int32), unseen
+
+
+def nb_csr_predict(X, off: torch.Tensor, vflat: torch.Tensor, delta: torch.Tensor, base: torch.Tensor):
+    """(index of the first maximal score per row (int32), lowest feature with an unseen value or
+    ``NB_NONE``) of a ``SparseColumn`` on the model's device. ``off`` [>= size + 1] / ``vflat``: the
+    features' sorted values; ``delta`` [ΣV, L]: log-probabilities relative to each feature's value 0;
+    ``base`` [L]. Raises ValueError for an index outside [0, size)."""
+    dev = delta.device
+    if dev.type != "cuda":
+        return torch_nb_csr_predict(X, off, vflat, delta, base)
+    from .csr import csr_arrays
+    from .kmeans import check_csr_error
+
+    n, D, L = len(X), X.size, int(base.numel())
+    indptr, idx, val = csr_arrays(X, torch.float64)
+    pred = torch.zeros(n, dtype=torch.int32, device=dev)
+    unseen = torch.full((1,), NB_NONE, dtype=torch.int32, device=dev)
+    holder = StoredCounts(None, None, None, None, torch.zeros(1, dtype=torch.int32, device=dev))
+    if n and D:
+        native.call("fmlx_nb_csr_predict", native.ptr(indptr), native.ptr(idx), native.ptr(val), n, D,
+                    native.ptr(off.to(torch.int64).contiguous()), native.ptr(vflat.contiguous()),
+                    native.ptr(delta.contiguous()), native.ptr(base.to(torch.float64).contiguous()), L, native.ptr(pred),
+                    native.ptr(unseen), native.ptr(holder.err), native.stream_ptr(dev))
+    check_csr_error(holder)
+    return pred, int(unseen.item())

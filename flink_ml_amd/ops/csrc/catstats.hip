@@ -19,6 +19,7 @@
 //   cs_codes   per tile: each entry's global distinct id (a block scan of the heads + the tile's
 //              carry) → codes[column][row], the distinct values and their columns;
 //   cs_chist   counts[code][label] of every (row, column) with integer atomics.
+#include "catkeys.h"
 #include "common.h"
 #include "scan.h"
 
@@ -264,17 +265,7 @@ __global__ __launch_bounds__(CS_THREADS) void cs_hist_kernel(const T* __restrict
 }
 
 // ---- general values: ordered keys of columns [j0, j0 + nc), sorted per column ----------------
-__device__ __forceinline__ uint64_t asc_key(double v) {
-  if (v == 0.0) v = 0.0;  // −0 → +0
-  uint64_t b = (uint64_t)__double_as_longlong(v);
-  if (v != v) b = 0x7ff8000000000000ull;
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_val(uint64_t k) {
-  const uint64_t b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  return __longlong_as_double((long long)b);
-}
-
+// (asc_key / key_val: catkeys.h)
 template <typename T>
 __global__ __launch_bounds__(CS_THREADS) void cs_col_keys_kernel(const T* __restrict__ X, long ld, long n, int j0,
                                                                  int nc, uint64_t* __restrict__ keys,
