@@ -49,7 +49,7 @@ template <int KS, bool FULL>
 // loads where they are issued (with restrict they get sunk next to their use, after the MFMAs).
 __global__ __launch_bounds__(256, 1) void kmeans_assign_bf16_kernel(const bf16_t* __restrict__ X, long ld, long n,
                                                                  int D, const bf16_t* Cb, const float* cnorm,
-                                                                 int kpad, int* __restrict__ labels) {
+                                                                 int kpad, int* __restrict__ labels, int base16) {
   constexpr int MT = KS <= 8 ? 2 : 1;     // 32-row m-tiles per wave
   constexpr int DP = KS * 16;             // padded feature dim
   constexpr int ROWB = DP * 2 + 16;       // padded LDS row stride (bytes): conflict-free b128 reads
@@ -83,7 +83,9 @@ __global__ __launch_bounds__(256, 1) void kmeans_assign_bf16_kernel(const bf16_t
       }
     }
   } else {
-    const bool aligned16 = (ld & 7) == 0;
+    // 16-byte loads need the base 16-byte aligned as well as the pitch (base16, from the launcher);
+    // a view that only guarantees ops/kmeans.py mfma_ok's 4-byte base takes the four 4-byte loads
+    const bool aligned16 = base16 && (ld & 7) == 0;
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
       const long row = rowbase + m * 32 + r32;
@@ -984,7 +986,10 @@ int launch_assign_bf16(const void* X, long ld, long n, int D, const void* Cb, co
   const long rows_per_block = 4 * 32 * MT;
   const int blocks = (int)((n + rows_per_block - 1) / rows_per_block);
   if (blocks == 0) return 0;
-  const bool full = D == 16 * KS && (ld % 8) == 0 && ((uintptr_t)X % 16) == 0;
+  // the narrowest A-fragment loads are 4 bytes wide (ops/kmeans.py mfma_ok asks for the same)
+  if ((ld & 1) != 0 || ((uintptr_t)X % 4) != 0) return -2;
+  const bool base16 = ((uintptr_t)X % 16) == 0;
+  const bool full = D == 16 * KS && (ld % 8) == 0 && base16;
   const bool pipe = full && g_km_pipe && baug != nullptr;
   if constexpr (KS == 4 || KS == 8) {
     if (pipe) {
@@ -996,7 +1001,7 @@ int launch_assign_bf16(const void* X, long ld, long n, int D, const void* Cb, co
   }
   return with_bool(full, [&](auto fl) {
     hipLaunchKernelGGL((kmeans_assign_bf16_kernel<KS, fl.value>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)X, ld, n,
-                       D, (const bf16_t*)Cb, cnorm, kpad, labels);
+                       D, (const bf16_t*)Cb, cnorm, kpad, labels, (int)base16);
     return (int)hipGetLastError();
   });
 }
@@ -1018,6 +1023,8 @@ FMLX_API int fmlx_kmeans_set_sched(int mode) {
 
 // KS = padded K-steps of 16 (one of 1..8,10,12,16; >= ceil(D/16)); Cb is [kpad][16*KS] zero-padded.
 // baug: kpad x 8 bytes of scratch for the pipelined kernel's B_aug rows (nullptr: plain loop)
+// X: 4-byte-aligned base and an even ld at the least (−2 otherwise); 16-byte loads are taken only
+// where base and pitch are both 16-byte aligned
 FMLX_API int fmlx_kmeans_assign_bf16(const void* X, long ld, long n, int D, int KS, const void* Cb, const float* cnorm,
                                      int kpad, int* labels, void* baug, void* stream) {
   hipStream_t s = (hipStream_t)stream;
