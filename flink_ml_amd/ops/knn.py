@@ -8,6 +8,10 @@ semantics — the k nearest training points per query, nearest first, ties to th
   ``TrainPack`` is the training matrix pre-arranged once per model for the kernel's tile copy.
 * ``topk_from_products(G, qn, tn, k)`` (any D, k ≤ 32): takes an fp32 product block
   ``G = Q·Tᵀ`` from a library GEMM and scans it once (the fallback for D > 128).
+
+``csr_products(Q, cm, q0, q1)`` (``csrc/knn_csr.hip``) forms that product block from two CSR
+operands instead, a block of query rows and the training set's column-major copy, for sparse
+feature columns that are not densified (``csr_route``, ``FMLX_KNN_CSR``).
 """
 from __future__ import annotations
 
@@ -186,3 +190,170 @@ def select_topk(G: torch.Tensor, qn: torch.Tensor, tn: torch.Tensor, k: int) -> 
         native.call("fmlx_knn_select", int(dt == torch.float64), native.ptr(G), G.stride(0), nq, n, native.ptr(qn),
                     native.ptr(tn), int(k), native.ptr(idx), k, native.stream_ptr(G.device))
     return idx
+
+
+# ---- CSR feature columns (csrc/knn_csr.hip): the product block of two CSR operands
+# FMLX_KNN_CSR: "0" = a SparseColumn is densified (the path before the CSR kernel), "1" = the CSR
+# route whenever csr_supported, "auto" = the CSR route when the dense training matrix n·D·elem
+# would exceed the HBM budget or the training set's density nnz / (n·D) is at most CSR_CROSSOVER.
+CSR_ROUTE = os.environ.get("FMLX_KNN_CSR", "auto")
+# training rows per block of the products kernel (32 KiB of LDS accumulators), and every tile
+# the library is built with (32 KiB and 8 KiB)
+CSR_TILE_ROWS = {torch.float32: 8192, torch.float64: 4096}
+CSR_TILE_ROWS_BUILT = {torch.float32: (2048, 8192), torch.float64: (1024, 4096)}
+# the highest density of the measured sweep (100,000 training rows x 4,096, 1,024 queries, fp32,
+# k = 5 and 100; scripts/bench_knn_sparse.py, profiles/r19/INDEX.md) at which the CSR transform beat
+# the densified one in both run orders for both k: 5.2 / 5.7 ms against 7.4 / 8.0 ms at 5 %; at
+# 20 % the dense route wins 9x (67 ms against 7.5 ms). Measured on the GPU only: the host route
+# follows the same constant unmeasured.
+CSR_CROSSOVER = 0.05
+
+
+def csr_supported(X, device) -> bool:
+    """The CSR route takes this training column: 32-bit rows / entries / indices and, on a GPU, the
+    column-major copy and its sort scratch within the HBM budget (on the host the route is the
+    torch formulation)."""
+    from ..table import SparseColumn
+
+    device = torch.device(device)
+    if not isinstance(X, SparseColumn):
+        return False
+    n, D, nnz = len(X), X.size, int(X.indices.numel())
+    if n < 1 or D < 1 or n >= 2 ** 31 or nnz >= 2 ** 31 or D >= 2 ** 31:
+        return False
+    if device.type != "cuda":
+        return True
+    from ..common.outofcore import hbm_budget
+
+    budget = hbm_budget(device)
+    es = 8 if X.values.dtype == torch.float64 else 4
+    need = nnz * (4 + es) * 2 + 16 * nnz + 8 * (n + D)
+    return budget is None or need <= budget
+
+
+def csr_route(X, device) -> bool:
+    """Whether a sparse training column takes the CSR route (``CSR_ROUTE``)."""
+    if CSR_ROUTE == "0" or not csr_supported(X, device):
+        return False
+    if CSR_ROUTE == "1":
+        return True
+    from .. import config
+    from ..common.outofcore import hbm_budget
+
+    device = torch.device(device)
+    n, D, nnz = len(X), X.size, int(X.indices.numel())
+    budget = hbm_budget(device) if device.type == "cuda" else None
+    if budget is not None and n * D * torch.empty(0, dtype=config.compute_dtype()).element_size() > budget:
+        return True
+    return nnz <= CSR_CROSSOVER * n * D
+
+
+class TorchColumnMajor:
+    """``ColumnMajor`` (ops/csr.py) formed by torch's stable sort, on the column's own device: the
+    host route's inverted index. An index outside [0, D) raises."""
+
+    def __init__(self, X):
+        self.n, self.D = len(X), X.size
+        idx = X.indices.long()
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= self.D):
+            raise ValueError("sparse feature index out of range [0, size)")
+        ptr = X.indptr.long()
+        rows = torch.repeat_interleave(torch.arange(self.n, device=idx.device), ptr[1:] - ptr[:-1])
+        order = torch.sort(idx, stable=True).indices
+        self.colptr = torch.zeros(self.D + 1, dtype=torch.int64, device=idx.device)
+        self.colptr[1:] = torch.cumsum(torch.bincount(idx, minlength=self.D), 0)
+        self.crow = rows[order].to(torch.int32)
+        self.cval = X.values[order]
+        self.nnz = int(idx.numel())
+
+
+def has_duplicate_index(cm) -> bool:
+    """Whether a row of the column-major copy ``cm`` stores an index twice: equal neighbouring rows
+    inside a column (the products kernel needs the rows of a column distinct)."""
+    if cm.nnz < 2:
+        return False
+    crow = cm.crow[: cm.nnz]
+    same = crow[1:] == crow[:-1]
+    starts = cm.colptr[1:-1]
+    starts = starts[(starts > 0) & (starts < cm.nnz)]
+    same[starts - 1] = False  # neighbours across a column boundary
+    return bool(same.any().item())
+
+
+def torch_products_csr(Q, T, dtype=torch.float64) -> torch.Tensor:
+    """``G[r, t] = Σ_e v_e · T[t, c_e]`` of two CSR columns as one index-add over the (query entry,
+    training entry) pairs that share a column, query entries in stored order: the host route and the
+    tests' second opinion. ``T``: a SparseColumn or its ``TorchColumnMajor``."""
+    cm = T if isinstance(T, TorchColumnMajor) else TorchColumnMajor(T)
+    if Q.size != cm.D:
+        raise ValueError("Vector size mismatched.")
+    nq, n = len(Q), cm.n
+    dev = cm.crow.device
+    G = torch.zeros(nq * n, dtype=dtype, device=dev)
+    qi = Q.indices.to(dev).long()
+    if qi.numel() == 0 or cm.nnz == 0:
+        return G.view(nq, n)
+    if int(qi.min()) < 0 or int(qi.max()) >= cm.D:
+        raise ValueError("sparse feature index out of range [0, size)")
+    qp = Q.indptr.to(dev).long()
+    qrow = torch.repeat_interleave(torch.arange(nq, device=dev), qp[1:] - qp[:-1])
+    lens = cm.colptr[qi + 1] - cm.colptr[qi]
+    ent = torch.repeat_interleave(torch.arange(qi.numel(), device=dev), lens)  # the pair's query entry
+    first = torch.cumsum(lens, 0) - lens
+    pos = cm.colptr[qi][ent] + (torch.arange(ent.numel(), device=dev) - first[ent])
+    prod = Q.values.to(device=dev, dtype=dtype)[ent] * cm.cval[pos].to(dtype)
+    G.index_add_(0, qrow[ent] * n + cm.crow[pos].long(), prod)
+    return G.view(nq, n)
+
+
+def csr_sqnorm(X, dtype=torch.float64, err: torch.Tensor = None) -> torch.Tensor:
+    """Σv² per row of a SparseColumn in stored-entry order, accumulated in fp64, as ``dtype`` (fp32
+    or fp64). On the GPU an index outside [0, size) adds nothing and sets ``err`` when given."""
+    n = len(X)
+    dev = X.values.device
+    if dev.type != "cuda":
+        v = X.values.to(torch.float64)
+        ptr = X.indptr.long()
+        rows = torch.repeat_interleave(torch.arange(n), ptr[1:] - ptr[:-1])
+        return torch.zeros(n, dtype=torch.float64).index_add_(0, rows, v * v).to(dtype)
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError("knn csr: norms are fp32 or fp64")
+    from .csr import csr_arrays
+
+    indptr, idx, val = csr_arrays(X, torch.float64 if X.values.dtype == torch.float64 else torch.float32)
+    out = torch.empty(n, dtype=dtype, device=dev)
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    native.call("fmlx_knn_csr_sqnorm", int(val.dtype == torch.float64), int(dtype == torch.float64), native.ptr(indptr),
+                native.ptr(idx), native.ptr(val), n, X.size, native.ptr(out), native.ptr(err), native.stream_ptr(dev))
+    return out
+
+
+def csr_products(Q, cm, q0: int, q1: int, out: torch.Tensor = None, tile: int = None) -> torch.Tensor:
+    """``G [q1 - q0, n]`` for the query rows [q0, q1) of a device SparseColumn ``Q`` (values in
+    ``cm``'s dtype) against the training set's ``ColumnMajor`` ``cm``, every element summed in the
+    query row's stored-entry order. A bad index is skipped and sets ``cm.err``
+    (``ops.kmeans.check_csr_error``). ``tile``: one of ``CSR_TILE_ROWS_BUILT`` (the result does not
+    depend on it)."""
+    nq, n, dt = int(q1) - int(q0), cm.n, cm.acc
+    if Q.size != cm.D:
+        raise ValueError("Vector size mismatched.")
+    if not (0 <= q0 <= q1 <= len(Q)) or Q.values.dtype != dt or not Q.values.is_cuda:
+        raise ValueError("knn csr products: rows [%d, %d) of %d, values %s against %s" % (q0, q1, len(Q),
+                                                                                         Q.values.dtype, dt))
+    tile = int(CSR_TILE_ROWS[dt] if tile is None else tile)
+    if tile not in CSR_TILE_ROWS_BUILT[dt]:
+        raise ValueError("knn csr products: no kernel with a tile of %d rows" % tile)
+    if out is None:
+        out = torch.empty((nq, n), dtype=dt, device=cm.crow.device)
+    if out.dtype != dt or out.shape != (nq, n) or out.stride(1) != 1:
+        raise ValueError("knn csr products: bad output block %s %s" % (tuple(out.shape), out.dtype))
+    if nq and n:
+        qptr, qidx = Q.indptr, Q.indices
+        if qptr.dtype != torch.int64 or qidx.dtype != torch.int32 or not qptr.is_contiguous():
+            raise ValueError("knn csr products: the query column is not in kernel form (ops.csr.csr_arrays)")
+        native.call("fmlx_knn_csr_products", int(dt == torch.float64), native.ptr(qptr), native.ptr(qidx),
+                    native.ptr(Q.values), int(q0), nq, cm.D, native.ptr(cm.colptr), native.ptr(cm.crow),
+                    native.ptr(cm.cval), n, cm.nnz, tile, native.ptr(out), out.stride(0), native.ptr(cm.err),
+                    native.stream_ptr(cm.crow.device))
+    return out
