@@ -10,8 +10,8 @@ is HBM → host memory → disk:
   that fit the HBM budget (``FMLX_HBM_BUDGET``, bytes, suffixes K/M/G/T) are copied to the device
   once and stay there; the others go into the native ``DataCache`` (``parallel/datacache.py``) —
   memory segments up to its host budget (``FMLX_HOST_CACHE_BUDGET``), files under
-  ``FMLX_DATA_CACHE_PATH`` beyond it. Memory segments are pinned in place
-  (``hipHostRegister``), so a cached batch is DMA'd straight from the cache, with no staging copy.
+  ``FMLX_DATA_CACHE_PATH`` beyond it. On a GPU the memory segments are allocated pinned
+  (``hipHostMalloc``), so a cached batch is DMA'd straight from the cache, with no staging copy.
 * ``BatchRing`` streams the non-resident batches through a ring of device slots on a dedicated
   copy stream: the copy of batch b waits only for the round that last used its slot (a
   device-side event wait), the round that reads it waits only for its copy, so H2D copies of
@@ -114,19 +114,14 @@ class BatchStore:
             self.resident[s:e].copy_(X[s:e], non_blocking=False)
         self.cache = None
         self.recs: List[int] = []
-        self._registered: List[int] = []
         if R < self.P:
             kw = {"memory_budget": host_budget if host_budget is not None else host_cache_budget()}
             if segment_bytes:
                 kw["segment_bytes"] = segment_bytes
-            self.cache = DataCache(path=cache_path, **kw)
+            self.cache = DataCache(path=cache_path, pinned=on_dev, **kw)  # DMA straight from the cache
             for b in range(R, self.P):
                 s, e = b * self.B, min(self.n, (b + 1) * self.B)
                 self.recs.append(self.cache.append(X[s:e].contiguous().view(torch.uint8).reshape(-1).numpy()))
-            if on_dev:
-                for p, cap in self.cache.memory_segments():  # DMA straight from the cache
-                    if native.kernels().fmlx_host_register(p, cap) == 0:
-                        self._registered.append(p)
 
     def rows(self, b: int) -> int:
         return min(self.n, (b + 1) * self.B) - b * self.B
@@ -147,9 +142,6 @@ class BatchStore:
         return st
 
     def close(self) -> None:
-        for p in self._registered:
-            native.kernels().fmlx_host_unregister(p)
-        self._registered = []
         if self.cache is not None:
             self.cache.close()
             self.cache = None
@@ -212,18 +204,13 @@ class SparseBatchStore:
         self.r_values = self.values_h[o:o + nz].to(self.device)
         self.cache = None
         self.recs: List[int] = []
-        self._registered: List[int] = []
         if R < self.P:
             kw = {"memory_budget": host_budget if host_budget is not None else host_cache_budget()}
             if segment_bytes:
                 kw["segment_bytes"] = segment_bytes
-            self.cache = DataCache(path=cache_path, **kw)
+            self.cache = DataCache(path=cache_path, pinned=self.device.type == "cuda", **kw)
             for b in range(R, self.P):
                 self.recs.append(self.cache.append(self._record(b)))
-            if self.device.type == "cuda":
-                for p, cap in self.cache.memory_segments():
-                    if native.kernels().fmlx_host_register(p, cap) == 0:
-                        self._registered.append(p)
 
     def _layout(self, rows: int, nz: int):
         o_idx = _align((rows + 1) * 8)
@@ -275,9 +262,6 @@ class SparseBatchStore:
         return st
 
     def close(self) -> None:
-        for p in self._registered:
-            native.kernels().fmlx_host_unregister(p)
-        self._registered = []
         if self.cache is not None:
             self.cache.close()
             self.cache = None

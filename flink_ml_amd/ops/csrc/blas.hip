@@ -561,13 +561,19 @@ FMLX_API int fmlx_csr_batch_bounds(const long* indptr, long n, long B, long P, l
 }
 
 // ---- host memory for the out-of-core trainers (common/outofcore.py) ---------------------------
-// pin / unpin an existing host range (the data cache's memory segments): the DMA engines then
-// copy batches straight from the cache, no staging copy
-FMLX_API int fmlx_host_register(void* p, long bytes) {
-  return (int)hipHostRegister(p, (size_t)bytes, hipHostRegisterDefault);
+// pinned host memory for the data cache's memory segments (fmlx_dc_set_allocator): the DMA engines
+// then copy batches straight from the cache, no staging copy. nullptr when it cannot be had (the
+// cache then writes that segment to a file); the failed call's error is not left for a later launch.
+FMLX_API void* fmlx_host_alloc(int64_t bytes) {
+  void* p = nullptr;
+  if (hipHostMalloc(&p, (size_t)bytes, hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  return p;
 }
-FMLX_API int fmlx_host_unregister(void* p) { return (int)hipHostUnregister(p); }
-// stream-ordered host → device copy from pinned (or registered) memory
+FMLX_API void fmlx_host_free(void* p) { (void)hipHostFree(p); }
+// stream-ordered host → device copy from pinned memory
 FMLX_API int fmlx_memcpy_h2d(void* dst, const void* src, long bytes, void* stream) {
   return (int)hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
 }

@@ -44,7 +44,23 @@ struct Cache {
   std::vector<Rec> recs;
   std::mutex mu;
   int next_file = 0;
+  // memory segments come from here: page-aligned pageable memory, or what fmlx_dc_set_allocator gave
+  void* (*alloc)(int64_t) = nullptr;
+  void (*release)(void*) = nullptr;
 };
+
+char* seg_alloc(Cache* c, int64_t cap) {
+  if (c->alloc) return (char*)c->alloc(cap);
+  void* p = nullptr;
+  return ::posix_memalign(&p, 4096, (size_t)cap) == 0 ? (char*)p : nullptr;
+}
+
+void seg_free(Cache* c, char* p) {
+  if (c->release)
+    c->release(p);
+  else
+    std::free(p);
+}
 
 std::string seg_path(Cache* c, int idx) {
   char buf[64];
@@ -87,7 +103,7 @@ int spill(Cache* c, int idx) {
   s.fd = ::open(s.file.c_str(), O_CREAT | O_TRUNC | O_RDWR, 0644);
   if (s.fd < 0) return -1;
   if (!write_all(s.fd, s.mem, s.used)) return -2;
-  std::free(s.mem);
+  seg_free(c, s.mem);
   s.mem = nullptr;
   c->mem_used -= s.cap;
   c->file_bytes += s.used;
@@ -98,9 +114,7 @@ int new_segment(Cache* c, int64_t need) {
   Segment s;
   const int64_t cap = need > c->seg_bytes ? need : c->seg_bytes;
   if (c->mem_used + cap <= c->mem_budget) {
-    // page-aligned: the out-of-core trainers pin memory segments in place (hipHostRegister)
-    void* p = nullptr;
-    s.mem = ::posix_memalign(&p, 4096, (size_t)cap) == 0 ? (char*)p : nullptr;
+    s.mem = seg_alloc(c, cap);
     if (s.mem) {
       s.cap = cap;
       c->mem_used += cap;
@@ -125,6 +139,19 @@ FMLX_API void* fmlx_dc_open(const char* dir, int64_t seg_bytes, int64_t mem_budg
   c->seg_bytes = seg_bytes > 0 ? seg_bytes : (int64_t)1 << 30;
   c->mem_budget = mem_budget;
   return c;
+}
+
+// Memory segments allocated from now on come from `alloc` (void* (*)(int64_t bytes), nullptr when it
+// cannot serve) and go back through `release` (void (*)(void*)): the out-of-core trainers pass the
+// kernel library's pinned-memory pair, so the DMA engines copy batches straight from the cache.
+// Only before the first append; returns 0, or -1 once a segment exists.
+FMLX_API int fmlx_dc_set_allocator(void* h, void* alloc, void* release) {
+  Cache* c = (Cache*)h;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->segs.empty() || !alloc || !release) return -1;
+  c->alloc = reinterpret_cast<void* (*)(int64_t)>(alloc);
+  c->release = reinterpret_cast<void (*)(void*)>(release);
+  return 0;
 }
 
 // Appends one record; returns its index (>= 0) or a negative error.
@@ -277,7 +304,7 @@ FMLX_API void* fmlx_dc_reopen(const char* dir) {
 FMLX_API void fmlx_dc_close(void* h, int remove) {
   Cache* c = (Cache*)h;
   for (auto& s : c->segs) {
-    if (s.mem) std::free(s.mem);
+    if (s.mem) seg_free(c, s.mem);
     if (s.fd >= 0) ::close(s.fd);
     if (remove && !s.file.empty()) ::unlink(s.file.c_str());
   }

@@ -44,12 +44,19 @@ class DataCache:
     """Append-only byte-record store; records are read back by index."""
 
     def __init__(self, path: Optional[str] = None, segment_bytes: int = DEFAULT_SEGMENT_BYTES,
-                 memory_budget: int = DEFAULT_MEMORY_BUDGET, _handle=None):
+                 memory_budget: int = DEFAULT_MEMORY_BUDGET, pinned: bool = False, _handle=None):
+        """``pinned``: memory segments are pinned host memory from the kernel library (a GPU copies
+        a record straight from ``record_ptr``)."""
         self.path = path or default_cache_dir()
         lib = native.host()
         self._h = _handle or lib.fmlx_dc_open(self.path.encode(), int(segment_bytes), int(memory_budget))
         if not self._h:
             raise RuntimeError("cannot open data cache at %s" % self.path)
+        if pinned:
+            k = native.kernels()
+            alloc, free = (ctypes.cast(f, ctypes.c_void_p).value for f in (k.fmlx_host_alloc, k.fmlx_host_free))
+            if lib.fmlx_dc_set_allocator(self._h, alloc, free) != 0:
+                raise RuntimeError("cannot set the data cache's allocator")
 
     @classmethod
     def reopen(cls, path: str) -> "DataCache":

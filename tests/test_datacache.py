@@ -36,6 +36,59 @@ def test_records_memory_then_files(tmp_path):
     assert not os.path.exists(str(tmp_path / "c"))
 
 
+def test_memory_segments_from_a_given_allocator(tmp_path):
+    """fmlx_dc_set_allocator: every memory segment comes from the given pair and goes back through
+    it (on spill and on close); an allocator that cannot serve sends the segment to a file; the
+    pair cannot change once a segment exists."""
+    import ctypes
+
+    from flink_ml_amd.ops import native
+
+    libc = ctypes.CDLL(None)
+    libc.malloc.restype, libc.malloc.argtypes = ctypes.c_void_p, [ctypes.c_size_t]
+    libc.free.restype, libc.free.argtypes = None, [ctypes.c_void_p]
+    live, served = set(), []
+
+    @ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_int64)
+    def alloc(n):
+        if len(served) >= 2:  # only two requests are served
+            served.append(None)
+            return None
+        p = libc.malloc(n)
+        live.add(p)
+        served.append(n)
+        return p
+
+    @ctypes.CFUNCTYPE(None, ctypes.c_void_p)
+    def release(p):
+        live.remove(p)
+        libc.free(p)
+
+    pair = [ctypes.cast(f, ctypes.c_void_p).value for f in (alloc, release)]
+    c = DataCache(str(tmp_path / "c"), segment_bytes=1000, memory_budget=10_000)
+    assert native.host().fmlx_dc_set_allocator(c._h, *pair) == 0
+    recs = [np.arange(i, i + 50, dtype=np.int64) for i in range(8)]  # 400 B each, 2 per segment
+    for r in recs:
+        c.append(r)
+    assert served == [1000, 1000, None, None] and len(live) == 2
+    assert native.host().fmlx_dc_set_allocator(c._h, *pair) == -1
+    st = c.stats()
+    assert st["memory_segments"] == 2 and st["file_bytes"] == 4 * 400
+    assert {p for p, _ in c.memory_segments()} == live and c.record_ptr(0) in live and c.record_ptr(7) is None
+    for i, r in enumerate(recs):
+        assert np.array_equal(np.frombuffer(c.read(i), np.int64), r)
+    c.spill()
+    assert not live and np.array_equal(np.frombuffer(c.read(1), np.int64), recs[1])
+    c.close()
+    c = DataCache(str(tmp_path / "d"), segment_bytes=1000, memory_budget=10_000)
+    assert native.host().fmlx_dc_set_allocator(c._h, *pair) == 0
+    del served[:]
+    c.append(recs[0])
+    assert len(live) == 1
+    c.close()
+    assert not live
+
+
 def _batches():
     g = torch.Generator().manual_seed(0)
     out = []

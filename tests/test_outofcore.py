@@ -86,6 +86,31 @@ def test_streamed_sgd_matches_in_hbm(budget_batches, host_budget, det, monkeypat
 
 
 @pytest.mark.gpu
+def test_ring_copies_from_the_cache_memory_segments(tmp_path):
+    """A GPU store's cached batches stay in (pinned) memory segments of the cache, none in files,
+    and the ring's copies straight out of them reproduce the partition over two passes."""
+    _need_gpu()
+    from flink_ml_amd.common import outofcore
+
+    n, d, B = 1003, 7, 97
+    X = torch.randn((n, d), generator=torch.Generator().manual_seed(1))
+    st = BatchStore(X, B, "cuda", (1 + outofcore.RING_SLOTS) * B * d * 4, cache_path=str(tmp_path / "c"),
+                    segment_bytes=3 * B * d * 4)
+    stats = st.stats()
+    assert st.R == 1 and stats["cache_memory_segments"] == 4 and stats["cache_file_bytes"] == 0
+    assert all(st.cache.record_ptr(st.record(b)) for b in range(st.R, st.P))
+    ring = outofcore.BatchRing(st)
+    for _ in range(2):
+        got = [st.resident_view(0).cpu()]
+        for b in range(1, st.P):
+            got.append(ring.fetch(b).cpu())
+            ring.release()
+        assert torch.equal(torch.cat(got), X)
+    assert ring.h2d_bytes == 2 * (n - B) * d * 4
+    st.close()
+
+
+@pytest.mark.gpu
 def test_logistic_regression_with_hbm_budget(monkeypatch):
     _need_gpu()
     from flink_ml_amd import Table
