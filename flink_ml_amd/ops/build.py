@@ -191,6 +191,9 @@ def _run(cmd):
 # per-source compiler options. kmeans.hip: MFMA accumulators in arch VGPRs — its epilogue reads
 # every accumulator with VALU ops each tile, and the AGPR form adds a v_accvgpr_read per value.
 FILE_FLAGS = {"kmeans.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-Wno-inline-asm"],
+              # likewise (64 accumulators read once per centroid pass); no packed-fp32 VALU forms
+              "kmeans_wide.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-Wno-inline-asm",
+                                  "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               # the fused round's ticket atomics: no lane-0 result fix-up (keeps counted vmcnt waits)
               "glm.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
               "glm_sparse.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],

@@ -62,6 +62,19 @@ def mfma_ok(X: torch.Tensor, metric: str) -> bool:
             and X.stride(1) == 1 and X.stride(0) % 2 == 0 and X.data_ptr() % 4 == 0 and mfma_ks(X.shape[1]) > 0)
 
 
+# bf16 euclidean rows of 256 < D <= 4096 (csrc/kmeans_wide.hip): the K-tiled MFMA assign and the
+# wide gather-sum. FMLX_KMEANS_WIDE=0: the route before them (fp32 copy + wave-per-row assign; no
+# round past D = 1024), for the A/B and the tests.
+WIDE = os.environ.get("FMLX_KMEANS_WIDE", "1") != "0"
+WIDE_MAX_D = 4096
+
+
+def mfma_wide_ok(X: torch.Tensor, metric: str) -> bool:
+    return (WIDE and X.device.type == "cuda" and X.dtype == torch.bfloat16 and metric == "euclidean"
+            and X.stride(1) == 1 and 256 < X.shape[1] <= WIDE_MAX_D and X.shape[1] % 8 == 0
+            and X.stride(0) % 8 == 0 and X.shape[1] <= X.stride(0) < (1 << 23) and X.data_ptr() % 16 == 0)
+
+
 class CentroidBuffers:
     """Device-side centroid representations consumed by the assign kernels."""
 
@@ -135,6 +148,10 @@ def assign(X: torch.Tensor, cb: CentroidBuffers, metric: str, out: torch.Tensor 
         native.call("fmlx_kmeans_assign_bf16", native.ptr(X), X.stride(0), n, D, cb.KS, native.ptr(cb.Cb),
                     native.ptr(cb.cnorm_b), cb.kpad, native.ptr(out), native.ptr(cb.baug), native.stream_ptr(X.device))
         return out
+    if mfma_wide_ok(X, metric):
+        native.call("fmlx_kmeans_assign_bf16_wide", native.ptr(X), X.stride(0), n, D, native.ptr(cb.Cb), cb.DP,
+                    native.ptr(cb.cnorm_b), cb.kpad, native.ptr(out), native.stream_ptr(X.device))
+        return out
     if X.dtype not in (torch.float32, torch.float64):
         X = X.to(torch.float32)
     X = X if X.stride(1) == 1 else X.contiguous()
@@ -203,6 +220,7 @@ class KMeansRound:
         self.zero_i64 = torch.zeros(1, dtype=torch.int64, device=dev)
         self.fast = (dev.type == "cuda" and X.dtype == torch.bfloat16 and self.D in (8, 16, 32, 64, 128, 256, 512)
                      and X.stride(1) == 1 and X.stride(0) % 8 == 0 and X.data_ptr() % 16 == 0)
+        self.wide = not self.fast and self.n > 0 and mfma_wide_ok(X, metric)
         lib = native.kernels() if dev.type == "cuda" else None
         self.stable = dev.type == "cuda" and GROUP_SORT and k <= lib.fmlx_group_stable_max_keys()
         self.group = (dev.type == "cuda" and GROUP_SORT and not self.stable and not DETERMINISTIC
@@ -264,6 +282,10 @@ class KMeansRound:
         offsets, chunk_off = self.offsets, self.chunk_off
         if self.fast:
             native.call("fmlx_kmeans_chunk_sum_bf16v", native.ptr(X), X.stride(0), self.D, native.ptr(self.order32),
+                        native.ptr(offsets), native.ptr(chunk_off), self.k, self.max_chunks, native.ptr(self.partial),
+                        stream)
+        elif self.wide:
+            native.call("fmlx_kmeans_chunk_sum_bf16w", native.ptr(X), X.stride(0), self.D, native.ptr(self.order32),
                         native.ptr(offsets), native.ptr(chunk_off), self.k, self.max_chunks, native.ptr(self.partial),
                         stream)
         else:
