@@ -9,7 +9,9 @@ fp32 by default / fp64 on CPU), ``dist = sqrt(|‖q‖² + ‖t‖² − 2 q·t|
 point wins, like the reference's strict-``>`` priority-queue replacement) and a majority vote.
 On the GPU (fp32, D ≤ 128, k ≤ 64) distances and top-k are ONE fused HIP kernel (fp32 matrix-core
 products, top-k in registers: the nq×n distance block never reaches HBM, ``ops/csrc/knn.hip``);
-wider features take the split path (library GEMM block + one top-k scan of it, k ≤ 16).
+rows of 128 < D ≤ 4096 (D % 4 == 0) take the K-tiled fused kernel of ``ops/csrc/knn_wide.hip``, which
+reads the row-major fp32 training matrix and query block as they are stored; everything else takes
+the split path (library GEMM block + one top-k scan or radix selection of it).
 Vote ties go to the tied label that occurs nearest to the query (resolved on the device, only
 for the rows that tie).
 
@@ -179,11 +181,12 @@ FUSED_QUERY_BLOCK = 1 << 18
 
 
 def knn_predict(Q: torch.Tensor, T: torch.Tensor, tnorm: torch.Tensor, labels: torch.Tensor, k: int,
-                block: int = 4096, pack=None, classes=None) -> torch.Tensor:
+                block: int = 4096, pack=None, classes=None, Tc=None) -> torch.Tensor:
     """Predicted labels of queries Q [nq, d] (a dense tensor, or a SparseColumn that is densified a
     query block at a time) against training points T [n, d]. ``pack``: a cached
     ``ops.knn.TrainPack`` of T for the fused GPU path (built here when not given); ``classes``:
-    the cached sorted distinct labels (a sort of all n labels otherwise)."""
+    the cached sorted distinct labels (a sort of all n labels otherwise); ``Tc``: the cached copy
+    of T in the compute dtype (made here when not given)."""
     dev = Q.device
     nq = len(Q)
     if isinstance(Q, SparseColumn) and Q.size != T.shape[1]:
@@ -204,11 +207,24 @@ def knn_predict(Q: torch.Tensor, T: torch.Tensor, tnorm: torch.Tensor, labels: t
                 idx = knn_ops.fused_topk(_query_rows(Q, s, s + fb, torch.float32), pack, kk)
                 out.append(knn_vote(labels[idx.long()], classes))
             return torch.cat(out) if out else torch.zeros(0, dtype=torch.float64, device=dev)
-    Tc = T.to(compute)
+    if Tc is None or Tc.dtype != compute:
+        Tc = T.to(compute)
     tn = tnorm.to(compute)
     if compute == torch.float32:
         from ..ops import knn as knn_ops
 
+        if knn_ops.wide_route(kk, T.shape[1]) and knn_ops.fused_wide_supported(kk, T.shape[0], T.shape[1], None, Tc):
+            # rows wider than the register-resident kernel's: the K-tiled fused kernel reads Tc and
+            # the query block as they are stored (csrc/knn_wide.hip)
+            tn32 = tn.contiguous()
+            fb = FUSED_QUERY_BLOCK if not isinstance(Q, SparseColumn) else knn_ops.query_block(T.shape[1])
+            for s in range(0, nq, fb):
+                q = _query_rows(Q, s, s + fb, torch.float32)
+                if not knn_ops.fused_wide_supported(kk, T.shape[0], T.shape[1], q, Tc):
+                    q = q.clone(memory_format=torch.contiguous_format)  # an odd pitch or base
+                idx = knn_ops.fused_wide_topk(q, Tc, tn32, kk)
+                out.append(knn_vote(labels[idx.long()], classes))
+            return torch.cat(out) if out else torch.zeros(0, dtype=torch.float64, device=dev)
         if kk <= knn_ops.ROUTE_MAX_K and knn_ops.supported(kk, T.shape[0], dev):
             tn32 = tn.contiguous()
             qb = knn_ops.query_block(T.shape[0])
@@ -306,17 +322,21 @@ class KnnModel(ModelWithData, KnnModelParams):
 
     def _predict_cache(self, T, tnorm, labels):
         """Per model data, built once: the fused kernel's tile-ordered copy of the training points
-        (GPU fp32 only) and the sorted distinct labels."""
+        (GPU fp32, D within the register-resident kernel's), for every other GPU model the copy of
+        T in the compute dtype that the wide fused kernel and the GEMM routes read, and the sorted
+        distinct labels."""
         from ..ops import knn as knn_ops
 
         cached = getattr(self, "_pack_cache", None)
         if cached is None or cached[0] is not T:
-            pack = None
+            pack = Tc = None
             if knn_ops.fused_supported(1, T.shape[0], T.shape[1], T.device) and config.acc_dtype() == torch.float32:
                 pack = knn_ops.TrainPack(T, tnorm)
-            cached = (T, pack, torch.unique(labels))
+            elif T.is_cuda:
+                Tc = T.to(config.acc_dtype())
+            cached = (T, pack, torch.unique(labels), Tc)
             self._pack_cache = cached
-        return cached[1], cached[2]
+        return cached[1], cached[2], cached[3]
 
     def transform(self, *inputs):
         t = inputs[0]
@@ -332,8 +352,8 @@ class KnnModel(ModelWithData, KnnModelParams):
             st = st.dense
         T, tnorm, labels = st
         Q = _query_matrix(t, fcol, T.device)
-        pack, classes = self._predict_cache(T, tnorm, labels)
-        pred = knn_predict(Q, T, tnorm, labels, self.get(self.K), pack=pack, classes=classes)
+        pack, classes, Tc = self._predict_cache(T, tnorm, labels)
+        pred = knn_predict(Q, T, tnorm, labels, self.get(self.K), pack=pack, classes=classes, Tc=Tc)
         return [t.with_column(self.get(self.PREDICTION_COL), pred.to(torch.float64))]
 
 

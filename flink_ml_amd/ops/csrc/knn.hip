@@ -20,55 +20,9 @@
 //     wave per row merges (stage 2); elements are admitted only below a wave-wide bound (see
 //     wave_bound) so the insertion sort rarely runs.
 #include "common.h"
-
-#include <math.h>
+#include "knn_list.h"  // lex_less, topk_insert, wave_merge_out, kth_entry, select32, topk_pop, the merge stage
 
 namespace {
-
-__device__ __forceinline__ bool lex_less(float da, int ia, float db, int ib) {
-  return da < db || (da == db && ia < ib);
-}
-
-template <int K>
-__device__ __forceinline__ void topk_insert(float (&bd)[K], int (&bi)[K], float d, int j) {
-  // (d, j) < tail already checked; drop the tail, bubble the new element up in (dist, index)
-  // order (an equal distance seen later keeps its place behind the earlier one)
-  bd[K - 1] = d;
-  bi[K - 1] = j;
-#pragma unroll
-  for (int i = K - 1; i > 0; --i) {
-    if (lex_less(bd[i], bi[i], bd[i - 1], bi[i - 1])) {
-      float td = bd[i]; bd[i] = bd[i - 1]; bd[i - 1] = td;
-      int ti = bi[i]; bi[i] = bi[i - 1]; bi[i - 1] = ti;
-    }
-  }
-}
-
-// Merge the 64 lane lists of one wave into the k best (dist, index) pairs, written with
-// stride 1 at od/oi (lane 0 writes).
-template <int K, bool SQRT>
-__device__ __forceinline__ void wave_merge_out(float (&bd)[K], int (&bi)[K], int lane, int k, float* od, int* oi) {
-  for (int t = 0; t < k; ++t) {
-    float wd = bd[0];
-    int wi = bi[0];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float xd = __shfl_xor(wd, off, 64);
-      const int xi = __shfl_xor(wi, off, 64);
-      if (lex_less(xd, xi, wd, wi)) { wd = xd; wi = xi; }
-    }
-    if (lane == 0) {
-      oi[t] = wi;
-      if (od) od[t] = SQRT ? __builtin_sqrtf(wd) : wd;
-    }
-    if (bi[0] == wi && wi != INT32_MAX) {  // (dist, index) pairs are unique: one lane pops
-#pragma unroll
-      for (int i = 0; i < K - 1; ++i) { bd[i] = bd[i + 1]; bi[i] = bi[i + 1]; }
-      bd[K - 1] = INFINITY;
-      bi[K - 1] = INT32_MAX;
-    }
-  }
-}
 
 // Ranking key |‖q‖² + ‖t‖² − 2·q·t|: sqrt is monotone, so the k nearest by key are the k nearest by
 // distance (ties → lower index either way); the sqrt is only taken for the k outputs.
@@ -190,28 +144,6 @@ __global__ __launch_bounds__(256) void knn_topk_scan_kernel(const float* __restr
     wave_merge_out<K, false>(bd, bi, lane, k, out_d + o, out_i + o);
 }
 
-// Stage 2: wave per row merges the S·k segment candidates (lexicographic (dist, index), so the
-// reference's tie rule survives the split).
-template <int K>
-__global__ __launch_bounds__(256) void knn_topk_merge_kernel(const float* __restrict__ cd, const int* __restrict__ ci,
-                                                             long nq, int S, int k, int* __restrict__ out_i,
-                                                             float* __restrict__ out_d) {
-  const int lane = threadIdx.x & 63;
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= nq) return;
-  float bd[K];
-  int bi[K];
-#pragma unroll
-  for (int i = 0; i < K; ++i) { bd[i] = INFINITY; bi[i] = INT32_MAX; }
-  const long m = (long)S * k;
-  for (long c = lane; c < m; c += 64) {
-    const float d = cd[row * m + c];
-    const int j = ci[row * m + c];
-    if (lex_less(d, j, bd[K - 1], bi[K - 1])) topk_insert<K>(bd, bi, d, j);
-  }
-  wave_merge_out<K, true>(bd, bi, lane, k, out_d ? out_d + row * k : nullptr, out_i + row * k);
-}
-
 template <int K>
 int launch_topk(const float* G, long ldg, long nq, long n, int S, const float* qn, const float* tn, int k, int* idx,
                 float* dist, float* ws_d, int* ws_i, hipStream_t s) {
@@ -224,8 +156,7 @@ int launch_topk(const float* G, long ldg, long nq, long n, int S, const float* q
                        k, si, sd);
     return 0;
   });
-  if (S > 1)
-    hipLaunchKernelGGL((knn_topk_merge_kernel<K>), dim3(blocks), dim3(256), 0, s, ws_d, ws_i, nq, S, k, idx, dist);
+  if (S > 1) launch_topk_merge<K>(ws_d, ws_i, nq, S, k, idx, dist, s);
   FMLX_CHECK_LAUNCH();
 }
 
@@ -258,34 +189,6 @@ int launch_topk(const float* G, long ldg, long nq, long n, int S, const float* q
 //    counts; their k-best candidates go through knn_topk_merge_kernel.
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
-
-// k-th entry (0-based k-1) of a sorted lane list, as a wave-uniform-index select
-template <int K>
-__device__ __forceinline__ void kth_entry(const float (&bd)[K], const int (&bi)[K], int k, float& td, int& ti) {
-  td = bd[0];
-  ti = bi[0];
-#pragma unroll
-  for (int i = 1; i < K; ++i)
-    if (i == k - 1) { td = bd[i]; ti = bi[i]; }
-}
-
-// v[b] for a per-lane b in [0, 32) as a linear select chain on register values. (A select TREE
-// gets folded into an indexed load of the array — select(load a, load b) → load(select) — which
-// demotes the whole key array to scratch.)
-__device__ __forceinline__ float select32(const float (&v)[32], int b) {
-  float r = INFINITY;
-#pragma unroll
-  for (int i = 0; i < 32; ++i) r = b == i ? v[i] : r;
-  return r;
-}
-
-template <int K>
-__device__ __forceinline__ void topk_pop(float (&bd)[K], int (&bi)[K]) {
-#pragma unroll
-  for (int i = 0; i < K - 1; ++i) { bd[i] = bd[i + 1]; bi[i] = bi[i + 1]; }
-  bd[K - 1] = INFINITY;
-  bi[K - 1] = INT32_MAX;
-}
 
 // floats per staged training tile: 128 (sub, h, row) rows of dp + 4 (the +4 pad keeps the b128
 // fragment reads conflict-free), then a 1-KiB block holding the 64 squared norms
@@ -456,9 +359,7 @@ int launch_fused(const float* Q, long ldq, long nq, int D, const float* Tt, long
   float* sd = S > 1 ? ws_d : dist;
   hipLaunchKernelGGL((knn_fused_kernel<K, DPMAX>), dim3(bq, S), dim3(256), 0, s, Q, ldq, nq, D, Tt, n, dp, k, S, si,
                      sd);
-  if (S > 1)
-    hipLaunchKernelGGL((knn_topk_merge_kernel<K>), dim3(fmlx_ceil_div(nq, 4)), dim3(256), 0, s, ws_d, ws_i, nq, S, k,
-                       idx, dist);
+  if (S > 1) launch_topk_merge<K>(ws_d, ws_i, nq, S, k, idx, dist, s);
   FMLX_CHECK_LAUNCH();
 }
 

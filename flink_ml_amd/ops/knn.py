@@ -6,6 +6,9 @@ semantics — the k nearest training points per query, nearest first, ties to th
 * ``fused_topk(Q, pack, k)`` (D ≤ 128, k ≤ 64): ONE kernel computes the distances on the fp32
   matrix cores and keeps the top-k in registers; the nq×n distance block never reaches HBM.
   ``TrainPack`` is the training matrix pre-arranged once per model for the kernel's tile copy.
+* ``fused_wide_topk(Q, T, tnorm, k)`` (128 < D ≤ 4096, D % 4 == 0, k ≤ 64): the same contract for
+  wider rows, K-tiled through an LDS ring straight from the row-major ``Q`` and ``T``
+  (``csrc/knn_wide.hip``; ``FMLX_KNN_WIDE``).
 * ``topk_from_products(G, qn, tn, k)`` (any D, k ≤ 32): takes an fp32 product block
   ``G = Q·Tᵀ`` from a library GEMM and scans it once (the fallback for D > 128).
 
@@ -106,6 +109,72 @@ def fused_topk(Q: torch.Tensor, pack: "TrainPack", k: int, with_dist: bool = Fal
     native.call("fmlx_knn_fused", native.ptr(Q), Q.stride(0), nq, d, native.ptr(pack.Tt), pack.n, pack.dp, k, S,
                 native.ptr(idx), native.ptr(dist), native.ptr(ws_d), native.ptr(ws_i), native.stream_ptr(Q.device))
     return (idx, dist) if with_dist else idx
+
+
+# ---- fused route for rows wider than FUSED_MAX_D (csrc/knn_wide.hip)
+# FMLX_KNN_WIDE: "1" = the wide fused kernel where it is supported and measured faster
+# (wide_route), "force" = wherever it is supported, "0" = the library-GEMM routes (kept for the A/B).
+WIDE = os.environ.get("FMLX_KNN_WIDE", "1")
+WIDE_MAX_D = 4096
+# (largest k of the class, widest D routed to the wide kernel): per list-length class the widest
+# row of the measured sweep (10,000 queries x 100,000 training rows, fp32, scripts/bench_knn_wide.py,
+# profiles/r21/knn_wide_ab.jsonl and INDEX.md) at which the fused transform beat GEMM + scan /
+# select in both run orders, with every narrower measured row winning too. k <= 16 wins at every
+# width up to 4096 (70.4 against 84.1 ms there at k = 16); k = 32 wins up to 1024 (21.7 against
+# 22.0 ms) and loses at 1536 (30.2 against 29.1); k = 64 wins up to 384 (12.4 against 12.7 ms) and
+# loses at 512 (14.6 against 14.5). The kernel itself accepts the whole range (fused_wide_supported).
+WIDE_ROUTE_MAX_D = ((16, 4096), (32, 1024), (64, 384))
+_WIDE_SLOTS = {}
+
+
+def _aligned_rows(X: torch.Tensor) -> bool:
+    """Rows the wide kernel's 16-byte LDS-DMA pieces can fetch: unit column stride, a pitch that is
+    a multiple of 4 floats (below 2^23) and a 16-byte aligned base."""
+    return (X.dim() == 2 and X.dtype == torch.float32 and X.stride(1) == 1 and X.stride(0) % 4 == 0
+            and X.shape[1] <= X.stride(0) < 2 ** 23 and X.data_ptr() % 16 == 0)
+
+
+def fused_wide_supported(k: int, n: int, d: int, Q: torch.Tensor, T: torch.Tensor) -> bool:
+    """The wide fused kernel takes this shape: fp32 device rows of FUSED_MAX_D < d <= WIDE_MAX_D,
+    d % 4 == 0, k within the list, and both operands 16-byte addressable as they are stored
+    (``Q`` None: the training side alone, for the route decision before a query block exists)."""
+    return (T.is_cuda and 1 <= k <= FUSED_MAX_K and k <= n < 2 ** 31 - 128
+            and FUSED_MAX_D < d <= WIDE_MAX_D and d % 4 == 0 and tuple(T.shape) == (n, d) and _aligned_rows(T)
+            and (Q is None or (Q.device == T.device and Q.shape[1] == d and _aligned_rows(Q))))
+
+
+def wide_route(k: int, d: int) -> bool:
+    """Whether KnnModel sends a shape the wide kernel supports to it (``WIDE``)."""
+    if WIDE == "0":
+        return False
+    return WIDE == "force" or any(k <= kc and d <= dmax for kc, dmax in WIDE_ROUTE_MAX_D)
+
+
+def fused_wide_topk(Q: torch.Tensor, T: torch.Tensor, tnorm: torch.Tensor, k: int, with_dist: bool = False,
+                    segments: int = 0):
+    """k nearest rows of ``T`` [n, D] (fp32, squared norms ``tnorm``) of every row of ``Q`` [nq, D]
+    in one fused kernel, both read as they are stored (row views with a pitch are fine)."""
+    if Q is None:
+        raise ValueError("knn fused wide: no queries")
+    nq, d = Q.shape
+    n = T.shape[0]
+    if tnorm.dtype != torch.float32 or tnorm.numel() != n or not fused_wide_supported(k, n, d, Q, T):
+        raise ValueError("knn fused wide: bad inputs Q=%s %s, T=%s %s, k=%d" % (tuple(Q.shape), Q.dtype,
+                                                                                tuple(T.shape), T.dtype, k))
+    tnorm = tnorm.contiguous()
+    if k not in _WIDE_SLOTS:
+        per_cu = native.kernels().fmlx_knn_fused_wide_blocks_per_cu(k)
+        _WIDE_SLOTS[k] = max(1, per_cu) * torch.cuda.get_device_properties(Q.device).multi_processor_count
+    S = int(segments) or fused_segments(nq, n, k, _WIDE_SLOTS[k])
+    idx = torch.empty((nq, k), dtype=torch.int32, device=Q.device)
+    dist = torch.empty((nq, k), dtype=torch.float32, device=Q.device) if with_dist else None
+    ws_d = torch.empty(nq * S * k, dtype=torch.float32, device=Q.device) if S > 1 else None
+    ws_i = torch.empty(nq * S * k, dtype=torch.int32, device=Q.device) if S > 1 else None
+    native.call("fmlx_knn_fused_wide", native.ptr(Q), Q.stride(0), nq, d, native.ptr(T), T.stride(0),
+                native.ptr(tnorm), n, k, S, native.ptr(idx), native.ptr(dist), native.ptr(ws_d), native.ptr(ws_i),
+                native.stream_ptr(Q.device))
+    return (idx, dist) if with_dist else idx
+
 
 MAX_K = 32
 # KnnModel routes k above this to the sort path: the per-lane insertion lists get long enough that
