@@ -62,10 +62,12 @@ def mfma_ok(X: torch.Tensor, metric: str) -> bool:
             and X.stride(1) == 1 and X.stride(0) % 2 == 0 and X.data_ptr() % 4 == 0 and mfma_ks(X.shape[1]) > 0)
 
 
-# bf16 euclidean rows of 256 < D <= 4096 (csrc/kmeans_wide.hip): the K-tiled MFMA assign and the
-# wide gather-sum. FMLX_KMEANS_WIDE=0: the route before them (fp32 copy + wave-per-row assign; no
-# round past D = 1024), for the A/B and the tests.
-WIDE = os.environ.get("FMLX_KMEANS_WIDE", "1") != "0"
+# bf16 euclidean rows of 256 < D <= 4096 (csrc/kmeans_wide.hip) and fp32 euclidean rows of
+# 128 < D <= 4096 (csrc/kmeans_wide_f32.hip): the K-tiled MFMA assign and the wide gather-sum.
+# FMLX_KMEANS_WIDE=0: the routes before them (bf16: an fp32 copy; then the GEMM + argmin block or
+# the wave-per-row assign; no round past D = 1024), for the A/B and the tests. =force: the fp32
+# assign takes the wide kernel at every shape it supports, whatever wide32_route measured.
+WIDE = {"0": False, "force": "force"}.get(os.environ.get("FMLX_KMEANS_WIDE", "1"), True)
 WIDE_MAX_D = 4096
 
 
@@ -73,6 +75,12 @@ def mfma_wide_ok(X: torch.Tensor, metric: str) -> bool:
     return (WIDE and X.device.type == "cuda" and X.dtype == torch.bfloat16 and metric == "euclidean"
             and X.stride(1) == 1 and 256 < X.shape[1] <= WIDE_MAX_D and X.shape[1] % 8 == 0
             and X.stride(0) % 8 == 0 and X.shape[1] <= X.stride(0) < (1 << 23) and X.data_ptr() % 16 == 0)
+
+
+def mfma_wide_f32_ok(X: torch.Tensor, metric: str) -> bool:
+    return (WIDE and X.device.type == "cuda" and X.dtype == torch.float32 and metric == "euclidean"
+            and X.stride(1) == 1 and 128 < X.shape[1] <= WIDE_MAX_D and X.shape[1] % 4 == 0
+            and X.stride(0) % 4 == 0 and X.shape[1] <= X.stride(0) < (1 << 23) and X.data_ptr() % 16 == 0)
 
 
 class CentroidBuffers:
@@ -87,6 +95,8 @@ class CentroidBuffers:
         self.cnorm = torch.zeros(k, dtype=acc_dtype, device=device)          # ‖c‖ (acc dtype)
         self.Cb = torch.zeros((self.kpad, self.DP), dtype=torch.bfloat16, device=device)
         self.cnorm_b = torch.full((self.kpad,), float("inf"), dtype=torch.float32, device=device)  # ‖c_bf16‖²
+        # ‖c‖² in fp32 for the wide fp32 assign, rewritten on the device by every launch of it
+        self.cnorm2 = torch.zeros(k, dtype=torch.float32, device=device)
         # the pipelined MFMA assign's B_aug rows (‖c‖² split into three bf16s), rebuilt from
         # cnorm_b by every assign launch
         self.baug = torch.empty(self.kpad * 2, dtype=torch.int32, device=device)
@@ -132,6 +142,30 @@ GEMM_ASSIGN_MAX_K = 64       # fp32 euclidean assign through a library GEMM up t
 GEMM_ASSIGN_ROWS = 1 << 22   # rows per GEMM chunk (bounds the n×k distance block)
 GEMM_ASSIGN_MIN_ROWS = 1 << 18  # below this the one-launch wave kernel wins (the GEMM path is ~6 launches)
 
+# Where the wide fp32 assign (csrc/kmeans_wide_f32.hip) takes over from the routes above: where it
+# beat them in both run orders (scripts/bench_kmeans_wide_f32.py, profiles/r22/INDEX.md; ms per
+# assign, new vs old). Its macro-tile is 128 centroids whatever k, so few centroids cost it as much
+# as 128 while the X stream bounds both sides.
+# Inside the GEMM's region (k <= GEMM_ASSIGN_MAX_K from GEMM_ASSIGN_MIN_ROWS rows), as (fewest
+# centroids, widest row) classes: at 1M rows k = 32 wins at D = 256 (0.54 vs 0.62) and loses at 512
+# (1.02 vs 0.77); k = 64 wins at 512 (1.03 vs 1.13) and loses at 768 (1.55 vs 1.40); k = 16 loses
+# at 256 (0.58 vs 0.39); k = 8 and k = 64 lose at 2048 and 4096 too (7.95 vs 4.96 at 4096, k = 64).
+WIDE32_OVER_GEMM = ((32, 256), (64, 512))
+# Below GEMM_ASSIGN_MIN_ROWS rows the wave-per-row kernel (D <= 1024) keeps up to this many
+# centroids: at 10,000 x 512 k = 16 loses (0.040 vs 0.033) and k = 32 wins (0.041 vs 0.046); at
+# 100,000 x 512 k = 8 loses (0.134 vs 0.113). Past D = 1024 the old route there is the
+# thread-per-row kernel, which loses at every measured k (100,000 x 2048, k = 8: 0.52 vs 6.9).
+WIDE32_WAVE_MAX_K = 16
+
+
+def wide32_route(n: int, D: int, k: int) -> bool:
+    """Whether ``assign`` sends a shape that ``mfma_wide_f32_ok`` accepts to the wide fp32 kernel."""
+    if WIDE == "force":
+        return True
+    if n >= GEMM_ASSIGN_MIN_ROWS and k <= GEMM_ASSIGN_MAX_K:
+        return any(k >= kmin and D <= dmax for kmin, dmax in WIDE32_OVER_GEMM)
+    return D > 1024 or k > WIDE32_WAVE_MAX_K
+
 
 def assign(X: torch.Tensor, cb: CentroidBuffers, metric: str, out: torch.Tensor = None) -> torch.Tensor:
     """Index of the closest centroid for every row (reference ``DistanceMeasure.findClosest``)."""
@@ -155,6 +189,13 @@ def assign(X: torch.Tensor, cb: CentroidBuffers, metric: str, out: torch.Tensor 
     if X.dtype not in (torch.float32, torch.float64):
         X = X.to(torch.float32)
     X = X if X.stride(1) == 1 else X.contiguous()
+    if mfma_wide_f32_ok(X, metric) and wide32_route(n, D, cb.k):
+        # fp32 MFMA keys ‖c‖² − 2·x·c with the argmin in registers (csrc/kmeans_wide_f32.hip); an
+        # fp64 centroid matrix is converted once per call, as the generic route does
+        C = cb.cent if cb.cent.dtype == torch.float32 else cb.cent.to(torch.float32)
+        native.call("fmlx_kmeans_assign_f32_wide", native.ptr(X), X.stride(0), n, D, native.ptr(C), C.stride(0),
+                    native.ptr(cb.cnorm2), cb.k, native.ptr(out), native.stream_ptr(X.device))
+        return out
     if X.dtype == torch.float32 and metric == "euclidean" and FP32_ASSIGN == "fused" and n >= GEMM_ASSIGN_MIN_ROWS:
         from . import knn as knn_ops
 
@@ -221,6 +262,7 @@ class KMeansRound:
         self.fast = (dev.type == "cuda" and X.dtype == torch.bfloat16 and self.D in (8, 16, 32, 64, 128, 256, 512)
                      and X.stride(1) == 1 and X.stride(0) % 8 == 0 and X.data_ptr() % 16 == 0)
         self.wide = not self.fast and self.n > 0 and mfma_wide_ok(X, metric)
+        self.wide32 = self.n > 0 and mfma_wide_f32_ok(X, metric)
         lib = native.kernels() if dev.type == "cuda" else None
         self.stable = dev.type == "cuda" and GROUP_SORT and k <= lib.fmlx_group_stable_max_keys()
         self.group = (dev.type == "cuda" and GROUP_SORT and not self.stable and not DETERMINISTIC
@@ -286,6 +328,10 @@ class KMeansRound:
                         stream)
         elif self.wide:
             native.call("fmlx_kmeans_chunk_sum_bf16w", native.ptr(X), X.stride(0), self.D, native.ptr(self.order32),
+                        native.ptr(offsets), native.ptr(chunk_off), self.k, self.max_chunks, native.ptr(self.partial),
+                        stream)
+        elif self.wide32:
+            native.call("fmlx_kmeans_chunk_sum_f32w", native.ptr(X), X.stride(0), self.D, native.ptr(self.order32),
                         native.ptr(offsets), native.ptr(chunk_off), self.k, self.max_chunks, native.ptr(self.partial),
                         stream)
         else:
