@@ -197,6 +197,9 @@ FILE_FLAGS = {"kmeans.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-Wno-inline-as
               # likewise, fp32 (64 accumulators read once per centroid macro-tile)
               "kmeans_wide_f32.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-Wno-inline-asm",
                                       "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              # likewise, fp64 (64 accumulator registers read once per centroid macro-tile)
+              "kmeans_wide_f64.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-Wno-inline-asm",
+                                      "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               # likewise (the accumulators become keys once per macro-tile)
               "knn_wide.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-Wno-inline-asm",
                                "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],

@@ -62,11 +62,13 @@ def mfma_ok(X: torch.Tensor, metric: str) -> bool:
             and X.stride(1) == 1 and X.stride(0) % 2 == 0 and X.data_ptr() % 4 == 0 and mfma_ks(X.shape[1]) > 0)
 
 
-# bf16 euclidean rows of 256 < D <= 4096 (csrc/kmeans_wide.hip) and fp32 euclidean rows of
-# 128 < D <= 4096 (csrc/kmeans_wide_f32.hip): the K-tiled MFMA assign and the wide gather-sum.
+# bf16 euclidean rows of 256 < D <= 4096 (csrc/kmeans_wide.hip), fp32 euclidean rows of
+# 128 < D <= 4096 (csrc/kmeans_wide_f32.hip) and fp64 euclidean rows of 16 <= D <= 4096
+# (csrc/kmeans_wide_f64.hip): the K-tiled MFMA assign and the wide gather-sum.
 # FMLX_KMEANS_WIDE=0: the routes before them (bf16: an fp32 copy; then the GEMM + argmin block or
-# the wave-per-row assign; no round past D = 1024), for the A/B and the tests. =force: the fp32
-# assign takes the wide kernel at every shape it supports, whatever wide32_route measured.
+# the wave-per-row assign; no round past D = 1024), for the A/B and the tests. =force: the fp32 and
+# fp64 assigns take the wide kernel at every shape it supports, whatever wide32_route and
+# wide64_route measured.
 WIDE = {"0": False, "force": "force"}.get(os.environ.get("FMLX_KMEANS_WIDE", "1"), True)
 WIDE_MAX_D = 4096
 
@@ -81,6 +83,12 @@ def mfma_wide_f32_ok(X: torch.Tensor, metric: str) -> bool:
     return (WIDE and X.device.type == "cuda" and X.dtype == torch.float32 and metric == "euclidean"
             and X.stride(1) == 1 and 128 < X.shape[1] <= WIDE_MAX_D and X.shape[1] % 4 == 0
             and X.stride(0) % 4 == 0 and X.shape[1] <= X.stride(0) < (1 << 23) and X.data_ptr() % 16 == 0)
+
+
+def mfma_wide_f64_ok(X: torch.Tensor, metric: str) -> bool:
+    return (WIDE and X.device.type == "cuda" and X.dtype == torch.float64 and metric == "euclidean"
+            and X.stride(1) == 1 and 16 <= X.shape[1] <= WIDE_MAX_D and X.shape[1] % 2 == 0
+            and X.stride(0) % 2 == 0 and X.shape[1] <= X.stride(0) < (1 << 22) and X.data_ptr() % 16 == 0)
 
 
 class CentroidBuffers:
@@ -167,6 +175,50 @@ def wide32_route(n: int, D: int, k: int) -> bool:
     return D > 1024 or k > WIDE32_WAVE_MAX_K
 
 
+# Where the wide fp64 assign (csrc/kmeans_wide_f64.hip) takes over from the wave-per-row kernel
+# (D <= 1024) and the thread-per-row kernel (wider): where it beat them in both run orders
+# (scripts/bench_kmeans_wide_f64.py, profiles/r23/INDEX.md; ms per assign, new vs old).
+# A block walks its 128 rows' whole K extent for a 64-centroid macro-tile whatever k, so its
+# latency is that of k = 64: few centroids on few rows stay on the wave-per-row kernel. As (fewest
+# rows, fewest centroids, widest row) classes for D <= 1024:
+#   1,000,000 rows: k = 2 wins at D = 16 (0.069 vs 0.472), 128 (0.325 vs 0.536), 512 (1.070 vs 1.156)
+#     and 1024 (2.096 vs 2.163); at 300,000 rows k = 2 loses at 512 (0.378 vs 0.351) and 1024
+#     (0.687 vs 0.662).
+#   100,000 rows: k = 8 wins at D = 16 (0.012 vs 0.140), 128 (0.042 vs 0.149), 512 (0.148 vs 0.287)
+#     and 1024 (0.295 vs 0.645); k = 2 loses at 512 (0.145 vs 0.121) and 1024 (0.284 vs 0.233).
+#   10,000 rows: k = 16 wins at D = 16 (0.012 vs 0.029), 128 (0.014 vs 0.033), 512 (0.045 vs 0.059)
+#     and 1024 (0.084 vs 0.123); k = 8 loses at 512 (0.044 vs 0.038) and 1024 (0.085 vs 0.073).
+#   1,000 rows: k = 64 wins at D = 16 (0.012 vs 0.028), 128 (0.014 vs 0.036) and 512 (0.044 vs 0.050)
+#     and loses at 1024 (0.084 vs 0.077); k = 16 loses at 16 (0.011 vs 0.009), 128 (0.014 vs 0.011)
+#     and 512 (0.044 vs 0.016).
+WIDE64_CLASSES = ((1_000_000, 2, 1024), (100_000, 8, 1024), (10_000, 16, 1024), (1_000, 64, 512))
+# Past D = 1024 the old route is the thread-per-row kernel, which lost at every measured shape:
+# 100 x 2048, k = 2: 0.162 vs 0.530; 100 x 4096, k = 2: 0.320 vs 1.065; 1,000 x 2048, k = 2: 0.164 vs
+# 0.810; 1M x 2048, k = 2: 4.15 vs 34.6; 1M x 2048, k = 1024: 76.7 ms vs 17.1 s.
+
+
+def wide64_route(n: int, D: int, k: int) -> bool:
+    """Whether ``assign`` sends a shape that ``mfma_wide_f64_ok`` accepts to the wide fp64 kernel."""
+    if WIDE == "force" or D > 1024:
+        return True
+    return any(n >= nmin and k >= kmin and D <= dmax for nmin, kmin, dmax in WIDE64_CLASSES)
+
+
+# The fp64 gather-sum (kmeans_chunk_sum_f64w_kernel) serves every round past D = 1024, where the
+# scalar-load chunk sum refuses the rows, and up to D = 1024 the rounds of at least this many rows:
+# with it the whole round won in both orders at every measured shape, whichever assign ran (10,000 x
+# 16, k = 2: 0.046 vs 0.062; 10,000 x 1024, k = 8: 0.140 vs 0.429; 1M x 1024, k = 1024: 39.3 vs 706).
+# It won at 1,000 rows too (1,000 x 512, k = 16: 0.090 vs 0.103 with the assign forced; 12-90 us per
+# round), but smaller rounds stay on fmlx_kmeans_chunk_sum: they are where its fp64 instantiation
+# is still exercised on every kind of strided view (tests/test_strided_views_gpu.py).
+WIDE64_SUM_MIN_ROWS = 10_000
+
+
+def wide64_sum_route(n: int, D: int) -> bool:
+    """Whether ``KMeansRound`` sums rows that ``mfma_wide_f64_ok`` accepts with the wide gather-sum."""
+    return WIDE == "force" or D > 1024 or n >= WIDE64_SUM_MIN_ROWS
+
+
 def assign(X: torch.Tensor, cb: CentroidBuffers, metric: str, out: torch.Tensor = None) -> torch.Tensor:
     """Index of the closest centroid for every row (reference ``DistanceMeasure.findClosest``)."""
     n, D = X.shape
@@ -195,6 +247,14 @@ def assign(X: torch.Tensor, cb: CentroidBuffers, metric: str, out: torch.Tensor 
         C = cb.cent if cb.cent.dtype == torch.float32 else cb.cent.to(torch.float32)
         native.call("fmlx_kmeans_assign_f32_wide", native.ptr(X), X.stride(0), n, D, native.ptr(C), C.stride(0),
                     native.ptr(cb.cnorm2), cb.k, native.ptr(out), native.stream_ptr(X.device))
+        return out
+    if mfma_wide_f64_ok(X, metric) and wide64_route(n, D, cb.k):
+        # fp64 MFMA keys max(0, ‖x‖² + ‖c‖² − 2·x·c) with the argmin in registers
+        # (csrc/kmeans_wide_f64.hip); fp32 centroid buffers are converted once per call
+        C = cb.cent.to(torch.float64)
+        cn = cb.cnorm.to(torch.float64)
+        native.call("fmlx_kmeans_assign_f64_wide", native.ptr(X), X.stride(0), n, D, native.ptr(C), C.stride(0),
+                    native.ptr(cn), cb.k, native.ptr(out), native.stream_ptr(X.device))
         return out
     if X.dtype == torch.float32 and metric == "euclidean" and FP32_ASSIGN == "fused" and n >= GEMM_ASSIGN_MIN_ROWS:
         from . import knn as knn_ops
@@ -263,6 +323,7 @@ class KMeansRound:
                      and X.stride(1) == 1 and X.stride(0) % 8 == 0 and X.data_ptr() % 16 == 0)
         self.wide = not self.fast and self.n > 0 and mfma_wide_ok(X, metric)
         self.wide32 = self.n > 0 and mfma_wide_f32_ok(X, metric)
+        self.wide64 = self.n > 0 and mfma_wide_f64_ok(X, metric) and wide64_sum_route(self.n, self.D)
         lib = native.kernels() if dev.type == "cuda" else None
         self.stable = dev.type == "cuda" and GROUP_SORT and k <= lib.fmlx_group_stable_max_keys()
         self.group = (dev.type == "cuda" and GROUP_SORT and not self.stable and not DETERMINISTIC
@@ -332,6 +393,10 @@ class KMeansRound:
                         stream)
         elif self.wide32:
             native.call("fmlx_kmeans_chunk_sum_f32w", native.ptr(X), X.stride(0), self.D, native.ptr(self.order32),
+                        native.ptr(offsets), native.ptr(chunk_off), self.k, self.max_chunks, native.ptr(self.partial),
+                        stream)
+        elif self.wide64:
+            native.call("fmlx_kmeans_chunk_sum_f64w", native.ptr(X), X.stride(0), self.D, native.ptr(self.order32),
                         native.ptr(offsets), native.ptr(chunk_off), self.k, self.max_chunks, native.ptr(self.partial),
                         stream)
         else:
