@@ -10,8 +10,11 @@ point wins, like the reference's strict-``>`` priority-queue replacement) and a 
 On the GPU (fp32, D ≤ 128, k ≤ 64) distances and top-k are ONE fused HIP kernel (fp32 matrix-core
 products, top-k in registers: the nq×n distance block never reaches HBM, ``ops/csrc/knn.hip``);
 rows of 128 < D ≤ 4096 (D % 4 == 0) take the K-tiled fused kernel of ``ops/csrc/knn_wide.hip``, which
-reads the row-major fp32 training matrix and query block as they are stored; everything else takes
-the split path (library GEMM block + one top-k scan or radix selection of it).
+reads the row-major fp32 training matrix and query block as they are stored; in the fp64 parity
+mode rows of even 16 ≤ D ≤ 4096 with k ≤ 32 take the fused fp64 MFMA kernel of
+``ops/csrc/knn_wide_f64.hip`` where ``ops.knn.f64_route`` holds (``FMLX_KNN_F64``); everything else
+(k beyond the lists, odd D or pitches, D < 16 or > 4096 in fp64, transforms below the route's floor)
+takes the split path (library GEMM block + one top-k scan or radix selection of it).
 Vote ties go to the tied label that occurs nearest to the query (resolved on the device, only
 for the rows that tie).
 
@@ -237,6 +240,19 @@ def knn_predict(Q: torch.Tensor, T: torch.Tensor, tnorm: torch.Tensor, labels: t
     if dev.type == "cuda":
         from ..ops import knn as knn_ops
 
+        if (compute == torch.float64 and knn_ops.f64_route(kk, nq, T.shape[0], T.shape[1])
+                and knn_ops.fused_f64_supported(kk, T.shape[0], T.shape[1], None, Tc)):
+            # parity mode: the fused fp64 MFMA kernel reads Tc and the query block as they are
+            # stored (csrc/knn_wide_f64.hip); no library GEMM, no product block
+            tnc = tn.contiguous()
+            fb = FUSED_QUERY_BLOCK if not isinstance(Q, SparseColumn) else knn_ops.query_block(T.shape[1])
+            for s in range(0, nq, fb):
+                q = _query_rows(Q, s, s + fb, torch.float64)
+                if not knn_ops.fused_f64_supported(kk, T.shape[0], T.shape[1], q, Tc):
+                    q = q.clone(memory_format=torch.contiguous_format)  # an odd pitch or base
+                idx = knn_ops.fused_f64_topk(q, Tc, tnc, kk)
+                out.append(knn_vote(labels[idx.long()], classes))
+            return torch.cat(out) if out else torch.zeros(0, dtype=torch.float64, device=dev)
         if knn_ops.select_supported(kk, T.shape[0], compute, dev):
             # k beyond the fused / scan kernels' lists, or fp64 (parity mode): library GEMM per
             # query block + the radix-select kernel (csrc/knn_select.hip)

@@ -203,6 +203,9 @@ FILE_FLAGS = {"kmeans.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-Wno-inline-as
               # likewise (the accumulators become keys once per macro-tile)
               "knn_wide.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-Wno-inline-asm",
                                "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              # likewise, fp64 (64 accumulator registers become keys once per macro-tile)
+              "knn_wide_f64.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-Wno-inline-asm",
+                                   "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               # the fused round's ticket atomics: no lane-0 result fix-up (keeps counted vmcnt waits)
               "glm.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
               "glm_sparse.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],

@@ -1,6 +1,6 @@
 """Bindings for ``csrc/knn.hip``: KNN predict's distances + per-query top-k (K13).
 
-Two device paths, both with ``KnnModel.predictLabel`` (reference ``KnnModel.java:154-194``)
+The device paths, all with ``KnnModel.predictLabel`` (reference ``KnnModel.java:154-194``)
 semantics — the k nearest training points per query, nearest first, ties to the lower index:
 
 * ``fused_topk(Q, pack, k)`` (D ≤ 128, k ≤ 64): ONE kernel computes the distances on the fp32
@@ -9,6 +9,9 @@ semantics — the k nearest training points per query, nearest first, ties to th
 * ``fused_wide_topk(Q, T, tnorm, k)`` (128 < D ≤ 4096, D % 4 == 0, k ≤ 64): the same contract for
   wider rows, K-tiled through an LDS ring straight from the row-major ``Q`` and ``T``
   (``csrc/knn_wide.hip``; ``FMLX_KNN_WIDE``).
+* ``fused_f64_topk(Q, T, tnorm, k)`` (fp64, even 16 ≤ D ≤ 4096, k ≤ 32): the same contract in the
+  fp64 parity mode on the fp64 matrix cores, key ``|(‖q‖² + ‖t‖²) − 2·q·t|`` as the select route
+  writes it (``csrc/knn_wide_f64.hip``; ``FMLX_KNN_F64``, ``f64_route``).
 * ``topk_from_products(G, qn, tn, k)`` (any D, k ≤ 32): takes an fp32 product block
   ``G = Q·Tᵀ`` from a library GEMM and scans it once (the fallback for D > 128).
 
@@ -76,13 +79,14 @@ class TrainPack:
         return self
 
 
-def fused_segments(nq: int, n: int, k: int, slots: int) -> int:
+def fused_segments(nq: int, n: int, k: int, slots: int, qrows: int = 128, tile: int = 64) -> int:
     """Training segments per query block. Cost model in tile units: the blocks run in
     ceil(blocks / slots) rounds of (tiles per segment + a list fill of ~1 + k/16 tiles); a bad
     split strands a mostly empty last round (782 query blocks × 2 segments on 512 slots ran 4
-    rounds for 3.05 rounds of work), so every S up to the cap is scored and the cheapest wins."""
-    bq = -(-nq // 128)
-    nt = -(-n // 64)
+    rounds for 3.05 rounds of work), so every S up to the cap is scored and the cheapest wins.
+    ``qrows`` / ``tile``: the kernel's queries per block and training rows per tile."""
+    bq = -(-nq // qrows)
+    nt = -(-n // tile)
     smax = int(max(1, min(FUSED_MAX_SEGMENTS, nt // FUSED_MIN_TILES, 256)))
     fill = 1.0 + k / 16.0
     best, best_cost = 1, None
@@ -171,6 +175,89 @@ def fused_wide_topk(Q: torch.Tensor, T: torch.Tensor, tnorm: torch.Tensor, k: in
     ws_d = torch.empty(nq * S * k, dtype=torch.float32, device=Q.device) if S > 1 else None
     ws_i = torch.empty(nq * S * k, dtype=torch.int32, device=Q.device) if S > 1 else None
     native.call("fmlx_knn_fused_wide", native.ptr(Q), Q.stride(0), nq, d, native.ptr(T), T.stride(0),
+                native.ptr(tnorm), n, k, S, native.ptr(idx), native.ptr(dist), native.ptr(ws_d), native.ptr(ws_i),
+                native.stream_ptr(Q.device))
+    return (idx, dist) if with_dist else idx
+
+
+# ---- fused route for fp64 rows, the parity mode (csrc/knn_wide_f64.hip)
+# FMLX_KNN_F64: "1" = the fp64 fused kernel where it is supported and measured faster (f64_route),
+# "force" = wherever it is supported, "0" = library GEMM + radix selection (kept for the A/B).
+F64 = os.environ.get("FMLX_KNN_F64", "1")
+F64_MAX_K = 32
+F64_MIN_D = 16
+F64_QUERY_ROWS = 64         # queries per block of the kernel
+F64_TILE = 128              # training rows per macro-tile
+# (fewest queries x training rows, largest k, widest D) of the classes routed to the fp64 kernel:
+# where the fused transform beat GEMM + radix selection in both run orders, every narrower measured
+# row of the class winning too (scripts/bench_knn_f64.py, profiles/r24/knn_f64_ab*.jsonl and
+# INDEX.md; ms per KnnModel.transform, new against old).
+#  * 2^26 pairs, k <= 5, D <= 256: 4,096 x 16,384 at k = 5: 0.33 against 0.73 (D 16), 0.89 against
+#    1.18 (D 256); D 1024 loses there (2.67 against 2.60) and at 10,000 x 10,000 (4.33 against 4.11).
+#  * 10^9 pairs (10,000 x 100,000), k <= 8, D <= 1024: 36.6 against 40.1 at k = 8, D 1024; k = 5
+#    loses at D 4096 (144 against 132).
+#  * 10^9 pairs, k <= 16, D <= 256: 14.0 against 16.5; D 512 wins by 1.7 % only (25.6 against 26.0)
+#    and is left out, D 1024 loses (48.3 against 39.7). Loses at 10^8 pairs (1.96 against 1.83).
+#  * 10^9 pairs, k <= 32, D <= 128: 10.8 against 14.2; D 256 loses (17.1 against 16.6). Loses at
+#    10^8 pairs (D 64: 1.52 against 1.32).
+F64_ROUTE_CLASSES = ((1 << 26, 5, 256), (10 ** 9, 8, 1024), (10 ** 9, 16, 256), (10 ** 9, 32, 128))
+# the fewest (query, training row) pairs any class routes: the kernel lost below it (2,048 x 8,192
+# x 256, k = 5: 0.62 against 0.50; 1,024 x 2,048: 0.62 against 0.36). Two reasons: a launch with a
+# few blocks is latency-bound (one block per 64 queries and segment walks its training rows alone),
+# and small fp64 transforms are where the select kernel stays exercised through the model
+# (tests/test_knn_gpu.py runs 301 x 6,000 on it). Never below 2^21.
+F64_ROUTE_MIN_PAIRS = 1 << 26
+_F64_SLOTS = {}
+
+
+def _aligned_rows_f64(X: torch.Tensor) -> bool:
+    """Rows the fp64 kernel's 16-byte LDS-DMA pieces can fetch (``ops.kmeans.mfma_wide_f64_ok``'s
+    alignment rules): unit column stride, an even pitch below 2^22 doubles, a 16-byte aligned base."""
+    return (X.dim() == 2 and X.dtype == torch.float64 and X.stride(1) == 1 and X.stride(0) % 2 == 0
+            and X.shape[1] <= X.stride(0) < 2 ** 22 and X.data_ptr() % 16 == 0)
+
+
+def fused_f64_supported(k: int, n: int, d: int, Q: torch.Tensor, T: torch.Tensor) -> bool:
+    """The fp64 fused kernel takes this shape: fp64 device rows of even F64_MIN_D <= d <= WIDE_MAX_D,
+    k within the list, and both operands 16-byte addressable as they are stored (``Q`` None: the
+    training side alone, for the route decision before a query block exists)."""
+    return (T.is_cuda and 1 <= k <= F64_MAX_K and k <= n < 2 ** 31 - 128
+            and F64_MIN_D <= d <= WIDE_MAX_D and d % 2 == 0 and tuple(T.shape) == (n, d) and _aligned_rows_f64(T)
+            and (Q is None or (Q.device == T.device and Q.shape[1] == d and _aligned_rows_f64(Q))))
+
+
+def f64_route(k: int, nq: int, n: int, d: int) -> bool:
+    """Whether KnnModel sends an fp64 shape the kernel supports to it (``F64``)."""
+    if F64 == "0":
+        return False
+    pairs = nq * n
+    return F64 == "force" or (pairs >= F64_ROUTE_MIN_PAIRS
+                              and any(pairs >= pc and k <= kc and d <= dmax for pc, kc, dmax in F64_ROUTE_CLASSES))
+
+
+def fused_f64_topk(Q: torch.Tensor, T: torch.Tensor, tnorm: torch.Tensor, k: int, with_dist: bool = False,
+                   segments: int = 0):
+    """k nearest rows of ``T`` [n, D] (fp64, squared norms ``tnorm``) of every row of ``Q`` [nq, D]
+    under ``|(‖q‖² + tnorm) − 2·q·t|`` in one fused kernel, both read as they are stored (row views
+    with a pitch are fine). int32 indices [nq, k], nearest first, ties to the lower index; a NaN key
+    is never chosen (with fewer than k other keys the last slots hold INT32_MAX)."""
+    if Q is None:
+        raise ValueError("knn fused f64: no queries")
+    nq, d = Q.shape
+    n = T.shape[0]
+    if tnorm.dtype != torch.float64 or tnorm.numel() != n or not fused_f64_supported(k, n, d, Q, T):
+        raise ValueError("knn fused f64: bad inputs Q=%s %s, T=%s %s, k=%d" % (tuple(Q.shape), Q.dtype,
+                                                                               tuple(T.shape), T.dtype, k))
+    tnorm = tnorm.contiguous()
+    if k not in _F64_SLOTS:
+        per_cu = native.kernels().fmlx_knn_fused_f64_blocks_per_cu(k)
+        _F64_SLOTS[k] = max(1, per_cu) * torch.cuda.get_device_properties(Q.device).multi_processor_count
+    S = int(segments) or fused_segments(nq, n, k, _F64_SLOTS[k], qrows=F64_QUERY_ROWS, tile=F64_TILE)
+    idx = torch.empty((nq, k), dtype=torch.int32, device=Q.device)
+    dist = torch.empty((nq, k), dtype=torch.float64, device=Q.device) if with_dist else None
+    ws_d = torch.empty(nq * S * k, dtype=torch.float64, device=Q.device) if S > 1 else None
+    ws_i = torch.empty(nq * S * k, dtype=torch.int32, device=Q.device) if S > 1 else None
+    native.call("fmlx_knn_fused_f64", native.ptr(Q), Q.stride(0), nq, d, native.ptr(T), T.stride(0),
                 native.ptr(tnorm), n, k, S, native.ptr(idx), native.ptr(dist), native.ptr(ws_d), native.ptr(ws_i),
                 native.stream_ptr(Q.device))
     return (idx, dist) if with_dist else idx
