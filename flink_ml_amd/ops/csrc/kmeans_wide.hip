@@ -1,8 +1,8 @@
-// KMeans for dense bf16 rows of 256 < D <= 4096 (euclidean): the K-tiled MFMA assign and the
-// update's wide gather-sum. kmeans.hip's MFMA assign keeps a wave's whole rows in registers and
-// stops at D = 256; here nothing row-sized stays in registers.
+// KMeans for dense bf16 rows of 256 < D <= 4096 (euclidean; cosine from D = 64): the K-tiled MFMA
+// assign and the update's wide gather-sum. kmeans.hip's MFMA assign keeps a wave's whole rows in
+// registers and stops at D = 256; here nothing row-sized stays in registers.
 //
-// kmeans_assign_bf16_wide_kernel
+// kmeans_assign_bf16_wide_kernel<COSINE> (the euclidean instantiation first)
 //  * A block of 256 threads owns 128 rows for the whole kernel, walks the centroids in passes of
 //    128 and K in chunks of 64 (4 steps of v_mfma_f32_32x32x16_bf16). The waves sit 2 x 2, each
 //    with 64 rows x 64 centroids of the pass as 2 x 2 accumulator tiles (64 fp32 registers); per
@@ -24,9 +24,17 @@
 //    the pieces of the last chunk past D are fetched from the chunk's first piece instead and
 //    zeroed in LDS by the lane that fetched them, in both operands, so they add exactly 0.
 //  * The K order within a (row, centroid) is fixed: labels do not depend on the grid.
+//  * COSINE: the same walk with key = acc / ‖c_bf16‖, i.e. −2·x·c/‖c‖. The pass's cn registers hold
+//    the scale 1/sqrt(‖c_bf16‖²), NaN for the padding (+inf), a zero and a NaN centroid, so none of
+//    them wins; the running index starts at −1. ‖x‖² of a row is summed once, during the first
+//    pass, from the A fragments (v_dot2_f32_bf16): the wn = 0 / 1 wave of a row pair takes A tile
+//    0 / 1, the two K halves meet by one exchange. The positive factor 1/‖x‖ does not move the
+//    argmin; it multiplies the winning key after the reduction, where 0·inf (a zero row) and inf·0
+//    (an inf element) are NaN like the key of a row with a NaN element: label −1, the generic
+//    kernels' result. The chunk walk wraps at one chunk per pass (D = 64).
 //
-// kmeans_chunk_sum_bf16w_kernel: kmeans_chunk_sum_bf16v_kernel's contract for any D % 8 == 0 up to
-// 4096 — a lane holds the 16-byte pieces lane, lane + 64, … of a row (PPL of them, a compile-time
+// kmeans_chunk_sum_bf16w_kernel (any metric): kmeans_chunk_sum_bf16v_kernel's contract for any
+// D % 8 == 0 up to 4096 — a lane holds the 16-byte pieces lane, lane + 64, … of a row (PPL of them, a compile-time
 // rung), a wave sums its stripe of the chunk's rows in row order with U rows' loads in flight, and
 // the four waves' sums are added in wave order.
 #include "common.h"
@@ -34,6 +42,7 @@
 namespace {
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
 constexpr int KW_ROWS = 128;             // rows per block = centroids per pass
@@ -46,6 +55,7 @@ constexpr int KW_PW = KW_TILEB / 1024 / 4;  // 1-KiB LDS-DMA pieces per wave and
 constexpr int KW_CH = 256;               // rows per gather chunk (ops/kmeans.py CHUNK)
 
 // Cb / cnorm are not __restrict__: the asm fills fence the norm loads where they are issued
+template <bool COSINE>
 __global__ __launch_bounds__(256, 2) void kmeans_assign_bf16_wide_kernel(const bf16_t* X, long ld, long n, int D,
                                                                          const bf16_t* Cb, int DP, const float* cnorm,
                                                                          int kpad, int* __restrict__ labels) {
@@ -112,7 +122,7 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_bf16_wide_kernel(const b
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       best[m][r] = __builtin_inff();
-      bidx[m][r] = 0;
+      bidx[m][r] = COSINE ? -1 : 0;
     }
     acc[m][0] = zero16;
     acc[m][1] = zero16;
@@ -126,6 +136,9 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_bf16_wide_kernel(const b
   int fp = 0, fkc = 1;    // the next chunk to fill
   if (fkc == NC) { fkc = 0; fp = 1; }
   float cn[2] = {0.f, 0.f};
+  // cosine: this lane's share (K half h) of ‖x‖² of row 64·wm + 32·wn + r32 = 32·wave + r32, from
+  // the A fragments of the first pass; the wn = 0 / 1 waves of a row pair take A tile 0 / 1
+  float xs = 0.f;
   for (int i = 0; i < T; ++i) {
     const int slot = i & 1;
     // this wave's share of chunk i has landed
@@ -147,6 +160,8 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_bf16_wide_kernel(const b
       for (int t = 0; t < 2; ++t) {
         const int c = p * KW_ROWS + 64 * wn + 32 * t + r32;
         cn[t] = c < kpad ? cnorm[c] : __builtin_inff();
+        // cosine: the scale 1/‖c_bf16‖; NaN for the padding (+inf), a zero and a NaN centroid
+        if constexpr (COSINE) cn[t] = (cn[t] > 0.f && cn[t] < __builtin_inff()) ? 1.0f / sqrtf(cn[t]) : __builtin_nanf("");
       }
     }
     if (i + 1 < T) {
@@ -163,6 +178,16 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_bf16_wide_kernel(const b
         a[t] = *reinterpret_cast<const bf16x8_t*>(sb + arow + t * 32 * KW_ROWB + po);
         b[t] = *reinterpret_cast<const bf16x8_t*>(sb + brow + t * 32 * KW_ROWB + po);
       }
+      if constexpr (COSINE) {
+        if (p == 0) {
+          const bf16x8_t aw = __builtin_amdgcn_readfirstlane(wn) ? a[1] : a[0];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const bf16x2_t a2 = {aw[2 * e], aw[2 * e + 1]};
+            xs = __builtin_amdgcn_fdot2_f32_bf16(a2, a2, xs, false);
+          }
+        }
+      }
 #pragma unroll
       for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -178,7 +203,7 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_bf16_wide_kernel(const b
         for (int m = 0; m < 2; ++m) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const float key = acc[m][t][r] + cn[t];
+            const float key = COSINE ? acc[m][t][r] * cn[t] : acc[m][t][r] + cn[t];
             const bool lt = key < best[m][r];
             best[m][r] = lt ? key : best[m][r];
             bidx[m][r] = lt ? c : bidx[m][r];
@@ -218,7 +243,17 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_bf16_wide_kernel(const b
   }
   const float ok = __shfl_xor(bk, 1, 64);
   const int oi = __shfl_xor(bi, 1, 64);
-  if (ok < bk || (ok == bk && oi < bi)) bi = oi;
+  if constexpr (COSINE) {
+    const bool lo = ok < bk || (ok == bk && oi < bi);
+    // row ρ = 32·wave + lane/2 has its ‖x‖² in lanes ρ mod 32 and ρ mod 32 + 32 of this wave. The
+    // positive factor 1/‖x‖ was left out of the running keys (it does not move the argmin); here it
+    // makes the key of a zero row (0·inf) and of a row with an inf element (inf·0) NaN: label −1
+    const float x2 = xs + __shfl_xor(xs, 32, 64);
+    const float kx = (lo ? ok : bk) * (1.0f / sqrtf(__shfl(x2, lane >> 1, 64)));
+    bi = kx == kx ? (lo ? oi : bi) : -1;
+  } else {
+    if (ok < bk || (ok == bk && oi < bi)) bi = oi;
+  }
   if (half == 0 && row0 + rho < n) labels[row0 + rho] = bi;
 }
 
@@ -319,7 +354,26 @@ FMLX_API int fmlx_kmeans_assign_bf16_wide(const void* X, long ld, long n, int D,
   if (n <= 0) return 0;
   const long blocks = (n + KW_ROWS - 1) / KW_ROWS;
   if (blocks > 0x7fffffffL) return -2;
-  hipLaunchKernelGGL(kmeans_assign_bf16_wide_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(kmeans_assign_bf16_wide_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)X, ld, n, D, (const bf16_t*)Cb, DP, cnorm, kpad, labels);
+  return (int)hipGetLastError();
+}
+
+// The cosine instantiation on the same operands: label = the lowest index among the minimal
+// −x·c_bf16 / ‖x‖ / ‖c_bf16‖ (NaN never wins), −1 for a row without a winner (‖x‖ zero, inf or NaN; no
+// centroid with a finite non-zero norm). Rows from D = 64: cosine has no narrow MFMA kernel, so the
+// pitch DP of the image may be any multiple of 16 from D (ops/kmeans.py pads it for D <= 256); the
+// image stays below 2^30 elements.
+FMLX_API int fmlx_kmeans_assign_bf16_wide_cos(const void* X, long ld, long n, int D, const void* Cb, int DP,
+                                              const float* cnorm, int kpad, int* labels, void* stream) {
+  if (D < 64 || D > 4096 || (D % 8) != 0 || (ld % 8) != 0 || ld < D || ld >= (1L << 23) ||
+      ((uintptr_t)X % 16) != 0 || ((uintptr_t)Cb % 16) != 0 || DP < D || (DP % 16) != 0 || kpad < 1 ||
+      (long)kpad * DP >= (1L << 30))
+    return -2;
+  if (n <= 0) return 0;
+  const long blocks = (n + KW_ROWS - 1) / KW_ROWS;
+  if (blocks > 0x7fffffffL) return -2;
+  hipLaunchKernelGGL(kmeans_assign_bf16_wide_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)X, ld, n, D, (const bf16_t*)Cb, DP, cnorm, kpad, labels);
   return (int)hipGetLastError();
 }

@@ -1,6 +1,6 @@
-// KMeans for dense fp32 rows of 128 < D <= 4096 (euclidean): the K-tiled fp32 MFMA assign and the
-// update's wide gather-sum. The fp32 routes before it are the fused KNN kernel with k = 1 (whole
-// rows in registers, D <= 128), a library GEMM + argmin block (k <= 64, many rows) and the
+// KMeans for dense fp32 rows of 128 < D <= 4096 (euclidean and cosine): the K-tiled fp32 MFMA assign
+// and the update's wide gather-sum (any metric). The fp32 routes before it are the fused KNN
+// kernel with k = 1 (whole rows in registers, D <= 128), a library GEMM + argmin block (k <= 64, many rows) and the
 // wave-per-row / thread-per-row kernels of kmeans.hip; kmeans_wide.hip is the bf16 counterpart.
 //
 // kmeans_assign_f32_wide_kernel: knn_wide.hip's tile geometry with an argmin instead of lists.
@@ -36,6 +36,13 @@
 //    the pieces of the last chunk past D are fetched from the chunk's first piece instead and
 //    zeroed in LDS by the lane that fetched them, in both operands: they add exactly 0.
 //  * The K order within a (row, centroid) is fixed: labels do not depend on the grid.
+//  * COSINE (kmeans_assign_f32_wide_kernel<true>): accumulators start at 0 and key = −x·c / ‖c‖.
+//    The LDS table holds the scale 1/sqrt(‖c‖²) (NaN for a zero and a NaN centroid: never wins) and
+//    is read by the epilogue, so it is published with the tile's second chunk, when every wave has
+//    left the previous tile's epilogue. ‖x‖² is summed from the B fragments during the first
+//    macro-tile; the two half-waves' shares meet with the candidates. 1/‖x‖ multiplies the winning
+//    key at the end (0·inf, inf·0 → NaN): a zero row and a row with an inf or NaN element get −1,
+//    the generic kernels' result; the running index starts at −1.
 //
 // kmeans_chunk_sum_f32w_kernel<PPL>: kmeans_chunk_sum_bf16w_kernel's contract for fp32 rows of any
 // D % 4 == 0 up to 4096 — int32 row order, a lane holds the 16-byte pieces lane, lane + 64, … of a
@@ -80,6 +87,7 @@ __global__ __launch_bounds__(256) void kmeans_cnorm2_f32_kernel(const float* __r
 }
 
 // X / C / cn2 are not __restrict__: the asm fills read them behind the compiler's back
+template <bool COSINE>
 __global__ __launch_bounds__(256, 2) void kmeans_assign_f32_wide_kernel(const float* X, long ld, long n, int D,
                                                                         const float* C, long ldc, const float* cn2,
                                                                         int k, int* __restrict__ labels) {
@@ -141,7 +149,8 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_f32_wide_kernel(const fl
 #define KF_NORM(P_) cn2[((P_) * KF_MT + (int)threadIdx.x) < k ? ((P_) * KF_MT + (int)threadIdx.x) : k - 1]
 
   float bk = __builtin_inff();  // this lane's best key of its row, over the centroids of its half
-  int bi = 0;
+  int bi = COSINE ? -1 : 0;
+  float xs = 0.f;  // cosine: this lane's share (the K indices of half h) of its row's ‖x‖²
 
   float cv = 0.f;  // the next macro-tile's norm of this thread's centroid, on its way to LDS
   if ((int)threadIdx.x < KF_MT) cv = KF_NORM(0);
@@ -168,7 +177,15 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_f32_wide_kernel(const fl
         *reinterpret_cast<uint4*>(lds + slot * KF_SLOTB + KF_TILEA + (wave + 4 * q) * 1024 + lane * 16) =
             make_uint4(0u, 0u, 0u, 0u);
     }
-    if (kc == 0 && (int)threadIdx.x < KF_MT) cnl[threadIdx.x] = cv;
+    if constexpr (COSINE) {
+      // the table holds the scale 1/‖c‖ (NaN for a zero and a NaN centroid) and is read by the
+      // epilogue after the tile's last chunk: it is published one barrier later, with chunk 1
+      // (NC >= 5), when every wave has left the previous tile's epilogue
+      if (kc == 1 && (int)threadIdx.x < KF_MT)
+        cnl[threadIdx.x] = (cv > 0.f && cv < __builtin_inff()) ? 1.0f / sqrtf(cv) : __builtin_nanf("");
+    } else {
+      if (kc == 0 && (int)threadIdx.x < KF_MT) cnl[threadIdx.x] = cv;
+    }
     // … and every wave's; every wave is past chunk i − 1, whose slot the next fill takes
     __syncthreads();
     if (i + 1 < iters) {
@@ -182,9 +199,14 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_f32_wide_kernel(const fl
       for (int t = 0; t < KF_NSUB; ++t)
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
-          const f32x4_t v = *reinterpret_cast<const f32x4_t*>(cnl + 32 * t + 8 * g4 + 4 * h);
+          if constexpr (COSINE) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) acc[t][4 * g4 + e] = -0.5f * v[e];
+            for (int e = 0; e < 4; ++e) acc[t][4 * g4 + e] = 0.f;
+          } else {
+            const f32x4_t v = *reinterpret_cast<const f32x4_t*>(cnl + 32 * t + 8 * g4 + 4 * h);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[t][4 * g4 + e] = -0.5f * v[e];
+          }
         }
     }
     const unsigned char* sb = lds + slot * KF_SLOTB;
@@ -195,6 +217,12 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_f32_wide_kernel(const fl
       f32x4_t a[KF_NSUB];
 #pragma unroll
       for (int t = 0; t < KF_NSUB; ++t) a[t] = *reinterpret_cast<const f32x4_t*>(sb + arow + t * 32 * KF_ROWB + po);
+      if constexpr (COSINE) {
+        if (p == 0) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) xs = __builtin_fmaf(b[e], b[e], xs);
+        }
+      }
 #pragma unroll
       for (int e = 0; e < 4; ++e)
 #pragma unroll
@@ -205,16 +233,34 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_f32_wide_kernel(const fl
     // ---- the macro-tile's keys in ascending centroid order under strict '<': the lowest index of
     // equal keys stays, a NaN key and a clamped centroid never win
     const int cb = p * KF_MT + 4 * h;
+    if constexpr (COSINE) {
+      // key = −x·c / ‖c‖; the positive factor 1/‖x‖ does not move the argmin and waits for the end
 #pragma unroll
-    for (int t = 0; t < KF_NSUB; ++t)
+      for (int t = 0; t < KF_NSUB; ++t)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int c = cb + 32 * t + (r & 3) + 8 * (r >> 2);
-        const float key = -2.0f * acc[t][r];
-        const bool lt = key < bk && c < k;
-        bk = lt ? key : bk;
-        bi = lt ? c : bi;
-      }
+        for (int g4 = 0; g4 < 4; ++g4) {
+          const f32x4_t v = *reinterpret_cast<const f32x4_t*>(cnl + 32 * t + 8 * g4 + 4 * h);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int c = cb + 32 * t + 8 * g4 + e;
+            const float key = -acc[t][4 * g4 + e] * v[e];
+            const bool lt = key < bk && c < k;
+            bk = lt ? key : bk;
+            bi = lt ? c : bi;
+          }
+        }
+    } else {
+#pragma unroll
+      for (int t = 0; t < KF_NSUB; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int c = cb + 32 * t + (r & 3) + 8 * (r >> 2);
+          const float key = -2.0f * acc[t][r];
+          const bool lt = key < bk && c < k;
+          bk = lt ? key : bk;
+          bi = lt ? c : bi;
+        }
+    }
     kc = 0;
     ++p;
   }
@@ -224,7 +270,16 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_f32_wide_kernel(const fl
   // ---- the two half-lanes of a row meet under (key, index) order; lane h == 0 writes
   const float ok = __shfl_xor(bk, 32, 64);
   const int oi = __shfl_xor(bi, 32, 64);
-  if (ok < bk || (ok == bk && oi < bi)) bi = oi;
+  if constexpr (COSINE) {
+    // 1/‖x‖ makes the key of a zero row (0·inf) and of a row with an inf element (inf·0) NaN, like
+    // that of a row with a NaN element: no winner, label −1
+    const bool lo = ok < bk || (ok == bk && oi < bi);
+    const float x2 = xs + __shfl_xor(xs, 32, 64);
+    const float kx = (lo ? ok : bk) * (1.0f / sqrtf(x2));
+    bi = kx == kx ? (lo ? oi : bi) : -1;
+  } else {
+    if (ok < bk || (ok == bk && oi < bi)) bi = oi;
+  }
   if (h == 0 && xrow < n) labels[xrow] = bi;
 }
 
@@ -305,15 +360,9 @@ __global__ __launch_bounds__(256) void kmeans_chunk_sum_f32w_kernel(const float*
   }
 }
 
-}  // namespace
-
-// The K-tiled fp32 MFMA assign: X [n, D] (pitch ld) and the centroids C [k, D] (pitch ldc) fp32
-// row-major; cn2 [k] receives ‖c‖² from a kernel launched in front of the assign on the same
-// stream. Label = the lowest index among the minimal keys ‖c‖² − 2·x·c (NaN counts as +inf; 0 if no
-// key is finite). −2 unless 128 < D <= 4096, D % 4 == 0, the pitches are multiples of 4 floats
-// below 2^23 (32-bit byte offsets inside a tile), X and C are 16-byte aligned and 1 <= k.
-FMLX_API int fmlx_kmeans_assign_f32_wide(const float* X, long ld, long n, int D, const float* C, long ldc, float* cn2,
-                                         int k, int* labels, void* stream) {
+template <bool COSINE>
+int kf_assign(const float* X, long ld, long n, int D, const float* C, long ldc, float* cn2, int k, int* labels,
+              void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (D <= 128 || D > 4096 || (D % 4) != 0 || ld < D || ldc < D || (ld % 4) != 0 || (ldc % 4) != 0 ||
       ld >= (1L << 23) || ldc >= (1L << 23) || ((uintptr_t)X % 16) != 0 || ((uintptr_t)C % 16) != 0 || k < 1 ||
@@ -323,9 +372,29 @@ FMLX_API int fmlx_kmeans_assign_f32_wide(const float* X, long ld, long n, int D,
   const long blocks = (n + KF_ROWS - 1) / KF_ROWS;
   if (blocks > 0x7fffffffL) return -2;
   hipLaunchKernelGGL(kmeans_cnorm2_f32_kernel, dim3(fmlx_ceil_div(k, 4)), dim3(256), 0, s, C, ldc, D, k, cn2);
-  hipLaunchKernelGGL(kmeans_assign_f32_wide_kernel, dim3((unsigned)blocks), dim3(256), 0, s, X, ld, n, D, C, ldc,
-                     (const float*)cn2, k, labels);
+  hipLaunchKernelGGL(kmeans_assign_f32_wide_kernel<COSINE>, dim3((unsigned)blocks), dim3(256), 0, s, X, ld, n, D, C,
+                     ldc, (const float*)cn2, k, labels);
   FMLX_CHECK_LAUNCH();
+}
+
+}  // namespace
+
+// The K-tiled fp32 MFMA assign: X [n, D] (pitch ld) and the centroids C [k, D] (pitch ldc) fp32
+// row-major; cn2 [k] receives ‖c‖² from a kernel launched in front of the assign on the same
+// stream. Label = the lowest index among the minimal keys ‖c‖² − 2·x·c (NaN counts as +inf; 0 if no
+// key is finite). −2 unless 128 < D <= 4096, D % 4 == 0, the pitches are multiples of 4 floats
+// below 2^23 (32-bit byte offsets inside a tile), X and C are 16-byte aligned and 1 <= k.
+FMLX_API int fmlx_kmeans_assign_f32_wide(const float* X, long ld, long n, int D, const float* C, long ldc, float* cn2,
+                                         int k, int* labels, void* stream) {
+  return kf_assign<false>(X, ld, n, D, C, ldc, cn2, k, labels, stream);
+}
+
+// The cosine instantiation, same operands and limits: label = the lowest index among the minimal
+// −x·c / ‖x‖ / ‖c‖ with ‖c‖² from cn2 (NaN never wins), −1 for a row without a winner (‖x‖ zero, inf
+// or NaN; no centroid with a finite non-zero norm).
+FMLX_API int fmlx_kmeans_assign_f32_wide_cos(const float* X, long ld, long n, int D, const float* C, long ldc,
+                                             float* cn2, int k, int* labels, void* stream) {
+  return kf_assign<true>(X, ld, n, D, C, ldc, cn2, k, labels, stream);
 }
 
 // fmlx_kmeans_chunk_sum_bf16w's contract (int32 row order, partial[max_chunks][D] fp32) for fp32

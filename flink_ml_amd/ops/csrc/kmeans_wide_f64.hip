@@ -1,5 +1,5 @@
-// KMeans for dense fp64 rows of 16 <= D <= 4096, D even (euclidean; FMLX_COMPUTE_DTYPE=fp64, the
-// parity mode): the K-tiled fp64 MFMA assign and the update's wide gather-sum. The fp64 routes
+// KMeans for dense fp64 rows of 16 <= D <= 4096, D even (euclidean and cosine;
+// FMLX_COMPUTE_DTYPE=fp64, the parity mode): the K-tiled fp64 MFMA assign and the update's wide gather-sum. The fp64 routes
 // before it are the wave-per-row / thread-per-row kernels of kmeans.hip; kmeans_wide.hip and
 // kmeans_wide_f32.hip are the bf16 and fp32 counterparts.
 //
@@ -43,6 +43,9 @@
 //    the pieces of the last chunk past D are fetched from the chunk's first piece instead and
 //    zeroed in LDS by the lane that fetched them, in both operands: they add exactly 0.
 //  * The K order within a (row, centroid) and within Σx² is fixed: labels do not depend on the grid.
+//  * COSINE (kmeans_assign_f64_kernel<true>): the generic kernels' 1 − x·c / pn / cn on the same
+//    accumulators, pn and norm table; NaN (a zero, inf or NaN row or centroid) never wins, and the
+//    running index starts at −1, the generic kernels' label for a row without a winner.
 //
 // kmeans_chunk_sum_f64w_kernel<PPL>: kmeans_chunk_sum_f32w_kernel's contract for fp64 rows of any
 // even D up to 4096 — int32 row order, a lane holds the 16-byte pieces lane, lane + 64, … of a row
@@ -68,6 +71,7 @@ constexpr int KD_SLOTB = KD_TILEA + KD_TILEB;  // the centroid tile, then the X 
 constexpr int KD_CH = 256;               // rows per gather chunk (ops/kmeans.py CHUNK)
 
 // X / C / cnorm are not __restrict__: the asm fills read them behind the compiler's back
+template <bool COSINE>
 __global__ __launch_bounds__(256, 2) void kmeans_assign_f64_kernel(const double* X, long ld, long n, int D,
                                                                    const double* C, long ldc, const double* cnorm,
                                                                    int k, int* __restrict__ labels) {
@@ -128,12 +132,13 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_f64_kernel(const double*
   // ‖c‖ of centroid threadIdx.x of macro-tile P_ (clamped like the rows)
 #define KD_NORM(P_) cnorm[((P_) * KD_MT + (int)threadIdx.x) < k ? ((P_) * KD_MT + (int)threadIdx.x) : k - 1]
 
-  double bk[2], xs[2], pp[2];  // per B tile: the lane's best key of its row, its share of Σx², pn·pn
+  // per B tile: the lane's best key of its row, its share of Σx², pn·pn (cosine: pn)
+  double bk[2], xs[2], pp[2];
   int bi[2];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     bk[j] = __builtin_huge_val();
-    bi[j] = 0;
+    bi[j] = COSINE ? -1 : 0;
     xs[j] = 0.0;
     pp[j] = 0.0;
   }
@@ -210,7 +215,7 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_f64_kernel(const double*
         s += __shfl_xor(s, 16, 64);
         s += __shfl_xor(s, 32, 64);
         const double pn = sqrt(s);
-        pp[j] = pn * pn;
+        pp[j] = COSINE ? pn : pn * pn;
       }
     }
     // ---- the macro-tile's keys in ascending centroid order under strict '<': the lowest index of
@@ -226,8 +231,14 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_f64_kernel(const double*
         const double cc = cn * cn;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          double d2 = pp[j] + cc - 2.0 * acc[t][j][q];
-          d2 = d2 < 0.0 ? 0.0 : d2;  // NaN stays NaN
+          double d2;
+          if constexpr (COSINE) {
+            // the generic kernels' expression: NaN (never wins) for a zero, inf or NaN row or centroid
+            d2 = 1.0 - acc[t][j][q] / pp[j] / cn;
+          } else {
+            d2 = pp[j] + cc - 2.0 * acc[t][j][q];
+            d2 = d2 < 0.0 ? 0.0 : d2;  // NaN stays NaN
+          }
           const bool lt = d2 < bk[j] && c < k;
           bk[j] = lt ? d2 : bk[j];
           bi[j] = lt ? c : bi[j];
@@ -334,6 +345,22 @@ __global__ __launch_bounds__(256) void kmeans_chunk_sum_f64w_kernel(const double
   }
 }
 
+template <bool COSINE>
+int kd_assign(const double* X, long ld, long n, int D, const double* C, long ldc, const double* cnorm, int k,
+              int* labels, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (D < 16 || D > 4096 || (D % 2) != 0 || ld < D || ldc < D || (ld % 2) != 0 || (ldc % 2) != 0 ||
+      ld >= (1L << 22) || ldc >= (1L << 22) || ((uintptr_t)X % 16) != 0 || ((uintptr_t)C % 16) != 0 || k < 1 ||
+      k > INT32_MAX - KD_MT || cnorm == nullptr)
+    return -2;
+  if (n <= 0) return 0;
+  const long blocks = (n + KD_ROWS - 1) / KD_ROWS;
+  if (blocks > 0x7fffffffL) return -2;
+  hipLaunchKernelGGL(kmeans_assign_f64_kernel<COSINE>, dim3((unsigned)blocks), dim3(256), 0, s, X, ld, n, D, C, ldc,
+                     cnorm, k, labels);
+  FMLX_CHECK_LAUNCH();
+}
+
 }  // namespace
 
 // The K-tiled fp64 MFMA assign: X [n, D] (pitch ld) and the centroids C [k, D] (pitch ldc) fp64
@@ -343,17 +370,14 @@ __global__ __launch_bounds__(256) void kmeans_chunk_sum_f64w_kernel(const double
 // a tile), X and C are 16-byte aligned and 1 <= k.
 FMLX_API int fmlx_kmeans_assign_f64_wide(const double* X, long ld, long n, int D, const double* C, long ldc,
                                          const double* cnorm, int k, int* labels, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (D < 16 || D > 4096 || (D % 2) != 0 || ld < D || ldc < D || (ld % 2) != 0 || (ldc % 2) != 0 ||
-      ld >= (1L << 22) || ldc >= (1L << 22) || ((uintptr_t)X % 16) != 0 || ((uintptr_t)C % 16) != 0 || k < 1 ||
-      k > INT32_MAX - KD_MT || cnorm == nullptr)
-    return -2;
-  if (n <= 0) return 0;
-  const long blocks = (n + KD_ROWS - 1) / KD_ROWS;
-  if (blocks > 0x7fffffffL) return -2;
-  hipLaunchKernelGGL(kmeans_assign_f64_kernel, dim3((unsigned)blocks), dim3(256), 0, s, X, ld, n, D, C, ldc, cnorm, k,
-                     labels);
-  FMLX_CHECK_LAUNCH();
+  return kd_assign<false>(X, ld, n, D, C, ldc, cnorm, k, labels, stream);
+}
+
+// The cosine instantiation, same operands and limits: label = the lowest index among the minimal
+// 1 − x·c / ‖x‖ / ‖c‖ (NaN never wins), −1 for a row without a key below +inf.
+FMLX_API int fmlx_kmeans_assign_f64_wide_cos(const double* X, long ld, long n, int D, const double* C, long ldc,
+                                             const double* cnorm, int k, int* labels, void* stream) {
+  return kd_assign<true>(X, ld, n, D, C, ldc, cnorm, k, labels, stream);
 }
 
 // fmlx_kmeans_chunk_sum_f32w's contract (int32 row order, partial[max_chunks][D] fp64) for fp64

@@ -62,31 +62,34 @@ def mfma_ok(X: torch.Tensor, metric: str) -> bool:
             and X.stride(1) == 1 and X.stride(0) % 2 == 0 and X.data_ptr() % 4 == 0 and mfma_ks(X.shape[1]) > 0)
 
 
-# bf16 euclidean rows of 256 < D <= 4096 (csrc/kmeans_wide.hip), fp32 euclidean rows of
-# 128 < D <= 4096 (csrc/kmeans_wide_f32.hip) and fp64 euclidean rows of 16 <= D <= 4096
-# (csrc/kmeans_wide_f64.hip): the K-tiled MFMA assign and the wide gather-sum.
+# bf16 rows of 256 < D <= 4096 (csrc/kmeans_wide.hip; cosine from D = 64, which has no narrow MFMA
+# kernel), fp32 rows of 128 < D <= 4096 (csrc/kmeans_wide_f32.hip) and fp64 rows of 16 <= D <= 4096
+# (csrc/kmeans_wide_f64.hip): the K-tiled MFMA assign, a euclidean and a cosine instantiation each,
+# and the wide gather-sum, which serves every metric (manhattan assigns stay on the generic kernel).
 # FMLX_KMEANS_WIDE=0: the routes before them (bf16: an fp32 copy; then the GEMM + argmin block or
 # the wave-per-row assign; no round past D = 1024), for the A/B and the tests. =force: the fp32 and
 # fp64 assigns take the wide kernel at every shape it supports, whatever wide32_route and
 # wide64_route measured.
 WIDE = {"0": False, "force": "force"}.get(os.environ.get("FMLX_KMEANS_WIDE", "1"), True)
 WIDE_MAX_D = 4096
+WIDE_METRICS = ("euclidean", "cosine")
 
 
 def mfma_wide_ok(X: torch.Tensor, metric: str) -> bool:
-    return (WIDE and X.device.type == "cuda" and X.dtype == torch.bfloat16 and metric == "euclidean"
-            and X.stride(1) == 1 and 256 < X.shape[1] <= WIDE_MAX_D and X.shape[1] % 8 == 0
+    return (WIDE and X.device.type == "cuda" and X.dtype == torch.bfloat16 and metric in WIDE_METRICS
+            and X.stride(1) == 1 and (63 if metric == "cosine" else 256) < X.shape[1] <= WIDE_MAX_D
+            and X.shape[1] % 8 == 0
             and X.stride(0) % 8 == 0 and X.shape[1] <= X.stride(0) < (1 << 23) and X.data_ptr() % 16 == 0)
 
 
 def mfma_wide_f32_ok(X: torch.Tensor, metric: str) -> bool:
-    return (WIDE and X.device.type == "cuda" and X.dtype == torch.float32 and metric == "euclidean"
+    return (WIDE and X.device.type == "cuda" and X.dtype == torch.float32 and metric in WIDE_METRICS
             and X.stride(1) == 1 and 128 < X.shape[1] <= WIDE_MAX_D and X.shape[1] % 4 == 0
             and X.stride(0) % 4 == 0 and X.shape[1] <= X.stride(0) < (1 << 23) and X.data_ptr() % 16 == 0)
 
 
 def mfma_wide_f64_ok(X: torch.Tensor, metric: str) -> bool:
-    return (WIDE and X.device.type == "cuda" and X.dtype == torch.float64 and metric == "euclidean"
+    return (WIDE and X.device.type == "cuda" and X.dtype == torch.float64 and metric in WIDE_METRICS
             and X.stride(1) == 1 and 16 <= X.shape[1] <= WIDE_MAX_D and X.shape[1] % 2 == 0
             and X.stride(0) % 2 == 0 and X.shape[1] <= X.stride(0) < (1 << 22) and X.data_ptr() % 16 == 0)
 
@@ -164,12 +167,30 @@ WIDE32_OVER_GEMM = ((32, 256), (64, 512))
 # 100,000 x 512 k = 8 loses (0.134 vs 0.113). Past D = 1024 the old route there is the
 # thread-per-row kernel, which loses at every measured k (100,000 x 2048, k = 8: 0.52 vs 6.9).
 WIDE32_WAVE_MAX_K = 16
+# Cosine has neither the GEMM nor the fused route: the wide kernel's cosine instantiation stands
+# against the generic kernels alone (wave-per-row to D = 1024, thread-per-row beyond) at every row
+# count (scripts/bench_kmeans_cosine.py, profiles/r25/INDEX.md; ms per assign, new vs old; all
+# measured, none inherited). As (fewest rows, fewest centroids, widest row) classes for D <= 1024:
+#   1,000,000 rows: k = 8 wins at D = 512 (1.04 vs 1.23) and loses at 1024 (2.10 vs 2.08); k = 2 loses
+#     at 512 (1.07 vs 0.56) and 1024 (2.03 vs 0.87); k = 64 wins at 256, 512 and 1024 (2.05 vs 15.9).
+#   100,000 rows: k = 16 wins at 512 (0.14 vs 0.26) and 1024 (0.27 vs 0.45); k = 8 loses at 512
+#     (0.139 vs 0.129).
+#   10,000 rows: k = 32 wins at 512 (0.041 vs 0.051) and 1024 (0.079 vs 0.089); k = 16 loses at 512
+#     (0.042 vs 0.037).
+#   1,000 rows: k = 128 wins at 512 (0.041 vs 0.068) and 1024 (0.077 vs 0.091); k = 64 loses at 512
+#     (0.041 vs 0.036).
+# Past D = 1024 it won at every measured shape (1,000 x 2048, k = 2: 0.147 vs 0.714; 1M x 2048,
+# k = 64: 4.06 vs 1044). The bf16 cosine instantiation is not routed: it won at every measured shape
+# down to 1,000 x 64, k = 2 (0.008 vs 0.014), the old route starting with an fp32 copy of the matrix.
+WIDE32_COS_CLASSES = ((1_000_000, 8, 512), (100_000, 16, 1024), (10_000, 32, 1024), (1_000, 128, 1024))
 
 
-def wide32_route(n: int, D: int, k: int) -> bool:
+def wide32_route(n: int, D: int, k: int, metric: str = "euclidean") -> bool:
     """Whether ``assign`` sends a shape that ``mfma_wide_f32_ok`` accepts to the wide fp32 kernel."""
     if WIDE == "force":
         return True
+    if metric == "cosine":
+        return D > 1024 or any(n >= nmin and k >= kmin and D <= dmax for nmin, kmin, dmax in WIDE32_COS_CLASSES)
     if n >= GEMM_ASSIGN_MIN_ROWS and k <= GEMM_ASSIGN_MAX_K:
         return any(k >= kmin and D <= dmax for kmin, dmax in WIDE32_OVER_GEMM)
     return D > 1024 or k > WIDE32_WAVE_MAX_K
@@ -192,16 +213,31 @@ def wide32_route(n: int, D: int, k: int) -> bool:
 #     and loses at 1024 (0.084 vs 0.077); k = 16 loses at 16 (0.011 vs 0.009), 128 (0.014 vs 0.011)
 #     and 512 (0.044 vs 0.016).
 WIDE64_CLASSES = ((1_000_000, 2, 1024), (100_000, 8, 1024), (10_000, 16, 1024), (1_000, 64, 512))
+# The cosine instantiation (two fp64 divisions per key in its epilogue, the generic kernels'
+# expression) against the same two kernels: the classes' D = 512 and 1024 corners measured again
+# under cosine (profiles/r25/INDEX.md) and came out where the euclidean ones are; the narrower rows
+# (D = 16, 128) of each class are inherited from the euclidean measurement.
+#   1,000,000 rows: k = 2 wins at D = 512 (1.10 vs 1.16) and 1024 (2.12 vs 2.19); at 300,000 rows
+#     k = 2 loses at 512 (0.368 vs 0.353).
+#   100,000 rows: k = 8 wins at 512 (0.150 vs 0.295) and 1024 (0.298 vs 0.664); k = 2 loses at 512
+#     (0.157 vs 0.122).
+#   10,000 rows: k = 16 wins at 512 (0.045 vs 0.064) and 1024 (0.085 vs 0.130); k = 8 loses at 512
+#     (0.045 vs 0.040).
+#   1,000 rows: k = 64 wins at 512 (0.045 vs 0.053) and loses at 1024 (0.085 vs 0.080); k = 32 loses
+#     at 512 (0.045 vs 0.029).
+# Past D = 1024: 1,000 x 2048, k = 2: 0.165 vs 0.871; 1M x 2048, k = 1024: 67.6 ms vs 17.3 s.
+WIDE64_COS_CLASSES = WIDE64_CLASSES
 # Past D = 1024 the old route is the thread-per-row kernel, which lost at every measured shape:
 # 100 x 2048, k = 2: 0.162 vs 0.530; 100 x 4096, k = 2: 0.320 vs 1.065; 1,000 x 2048, k = 2: 0.164 vs
 # 0.810; 1M x 2048, k = 2: 4.15 vs 34.6; 1M x 2048, k = 1024: 76.7 ms vs 17.1 s.
 
 
-def wide64_route(n: int, D: int, k: int) -> bool:
+def wide64_route(n: int, D: int, k: int, metric: str = "euclidean") -> bool:
     """Whether ``assign`` sends a shape that ``mfma_wide_f64_ok`` accepts to the wide fp64 kernel."""
     if WIDE == "force" or D > 1024:
         return True
-    return any(n >= nmin and k >= kmin and D <= dmax for nmin, kmin, dmax in WIDE64_CLASSES)
+    classes = WIDE64_COS_CLASSES if metric == "cosine" else WIDE64_CLASSES
+    return any(n >= nmin and k >= kmin and D <= dmax for nmin, kmin, dmax in classes)
 
 
 # The fp64 gather-sum (kmeans_chunk_sum_f64w_kernel) serves every round past D = 1024, where the
@@ -234,26 +270,29 @@ def assign(X: torch.Tensor, cb: CentroidBuffers, metric: str, out: torch.Tensor 
         native.call("fmlx_kmeans_assign_bf16", native.ptr(X), X.stride(0), n, D, cb.KS, native.ptr(cb.Cb),
                     native.ptr(cb.cnorm_b), cb.kpad, native.ptr(out), native.ptr(cb.baug), native.stream_ptr(X.device))
         return out
+    # the wide kernels' cosine instantiations take the euclidean ones' operands (keys −x·c/‖x‖/‖c‖, −1
+    # for a row without a winner, like the generic kernels)
+    cos = "_cos" if metric == "cosine" else ""
     if mfma_wide_ok(X, metric):
-        native.call("fmlx_kmeans_assign_bf16_wide", native.ptr(X), X.stride(0), n, D, native.ptr(cb.Cb), cb.DP,
+        native.call("fmlx_kmeans_assign_bf16_wide" + cos, native.ptr(X), X.stride(0), n, D, native.ptr(cb.Cb), cb.DP,
                     native.ptr(cb.cnorm_b), cb.kpad, native.ptr(out), native.stream_ptr(X.device))
         return out
     if X.dtype not in (torch.float32, torch.float64):
         X = X.to(torch.float32)
     X = X if X.stride(1) == 1 else X.contiguous()
-    if mfma_wide_f32_ok(X, metric) and wide32_route(n, D, cb.k):
+    if mfma_wide_f32_ok(X, metric) and wide32_route(n, D, cb.k, metric):
         # fp32 MFMA keys ‖c‖² − 2·x·c with the argmin in registers (csrc/kmeans_wide_f32.hip); an
         # fp64 centroid matrix is converted once per call, as the generic route does
         C = cb.cent if cb.cent.dtype == torch.float32 else cb.cent.to(torch.float32)
-        native.call("fmlx_kmeans_assign_f32_wide", native.ptr(X), X.stride(0), n, D, native.ptr(C), C.stride(0),
+        native.call("fmlx_kmeans_assign_f32_wide" + cos, native.ptr(X), X.stride(0), n, D, native.ptr(C), C.stride(0),
                     native.ptr(cb.cnorm2), cb.k, native.ptr(out), native.stream_ptr(X.device))
         return out
-    if mfma_wide_f64_ok(X, metric) and wide64_route(n, D, cb.k):
+    if mfma_wide_f64_ok(X, metric) and wide64_route(n, D, cb.k, metric):
         # fp64 MFMA keys max(0, ‖x‖² + ‖c‖² − 2·x·c) with the argmin in registers
         # (csrc/kmeans_wide_f64.hip); fp32 centroid buffers are converted once per call
         C = cb.cent.to(torch.float64)
         cn = cb.cnorm.to(torch.float64)
-        native.call("fmlx_kmeans_assign_f64_wide", native.ptr(X), X.stride(0), n, D, native.ptr(C), C.stride(0),
+        native.call("fmlx_kmeans_assign_f64_wide" + cos, native.ptr(X), X.stride(0), n, D, native.ptr(C), C.stride(0),
                     native.ptr(cn), cb.k, native.ptr(out), native.stream_ptr(X.device))
         return out
     if X.dtype == torch.float32 and metric == "euclidean" and FP32_ASSIGN == "fused" and n >= GEMM_ASSIGN_MIN_ROWS:
@@ -321,9 +360,11 @@ class KMeansRound:
         self.zero_i64 = torch.zeros(1, dtype=torch.int64, device=dev)
         self.fast = (dev.type == "cuda" and X.dtype == torch.bfloat16 and self.D in (8, 16, 32, 64, 128, 256, 512)
                      and X.stride(1) == 1 and X.stride(0) % 8 == 0 and X.data_ptr() % 16 == 0)
-        self.wide = not self.fast and self.n > 0 and mfma_wide_ok(X, metric)
-        self.wide32 = self.n > 0 and mfma_wide_f32_ok(X, metric)
-        self.wide64 = self.n > 0 and mfma_wide_f64_ok(X, metric) and wide64_sum_route(self.n, self.D)
+        # the wide gather-sums do not see the metric: every metric's round takes them at the
+        # euclidean assign's shapes (without them no round past D = 1024)
+        self.wide = not self.fast and self.n > 0 and mfma_wide_ok(X, "euclidean")
+        self.wide32 = self.n > 0 and mfma_wide_f32_ok(X, "euclidean")
+        self.wide64 = self.n > 0 and mfma_wide_f64_ok(X, "euclidean") and wide64_sum_route(self.n, self.D)
         lib = native.kernels() if dev.type == "cuda" else None
         self.stable = dev.type == "cuda" and GROUP_SORT and k <= lib.fmlx_group_stable_max_keys()
         self.group = (dev.type == "cuda" and GROUP_SORT and not self.stable and not DETERMINISTIC
