@@ -265,7 +265,9 @@ __global__ __launch_bounds__(256, 1) void kmeans_assign_bf16_kernel(const bf16_t
       const unsigned long long hit = __ballot(v0 == v);
       const unsigned lo = (unsigned)hit, hi = (unsigned)(hit >> 32);
       const int l0 = __builtin_ctz(lo | 0x80000000u), l1 = __builtin_ctz(hi | 0x80000000u);
-      const int id = (int)(v & tmask) * 32 + (h ? l1 : l0);
+      // a row whose smallest key is +inf or NaN (an inf or NaN element in the row; every centroid NaN or
+      // padding) has no winner: label 0, like findClosest's bestIndex = 0
+      const int id = v >= 0x7F800000u ? 0 : (int)(v & tmask) * 32 + (h ? l1 : l0);
       if (r32 == r) mine = id;
     }
     if (r32 < 16) {
@@ -587,7 +589,8 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void kmeans_assign_bf16_pipe_kerne
 #pragma unroll
   for (int c = 31; c >= 0; --c) col = key[c] == mn ? c : col;
   const long row = rowbase + lane;
-  if (row < n) labels[row] = (int)(mn & tmask) * 32 + col;
+  // (no key below +inf: no winner, label 0 — as in kmeans_assign_bf16_kernel)
+  if (row < n) labels[row] = mn >= 0x7F800000u ? 0 : (int)(mn & tmask) * 32 + col;
   KM_STAMP(3)
 }
 
@@ -623,7 +626,7 @@ __global__ __launch_bounds__(256) void kmeans_assign_generic_kernel(const T* __r
       T dot = 0;
       for (int j = 0; j < D; ++j) dot += x[j] * c[j];
       T d2 = pn * pn + cn * cn - (T)2 * dot;
-      d2 = d2 > (T)0 ? d2 : (T)0;
+      d2 = d2 < (T)0 ? (T)0 : d2;  // max(0, d2); NaN stays NaN and never wins
       if (d2 < best) { best = d2; bi = i; }
     } else if (metric == 1) {
       T s = 0;
@@ -722,7 +725,7 @@ __global__ __launch_bounds__(256) void kmeans_assign_wave_kernel(const T* __rest
         if (metric == 0) {
           const T cn = Np[i];
           dist = pn * pn + cn * cn - (T)2 * acc[g];
-          dist = dist > (T)0 ? dist : (T)0;
+          dist = dist < (T)0 ? (T)0 : dist;  // max(0, dist); NaN stays NaN and never wins
         } else if (metric == 1) {
           dist = acc[g];
         } else {
@@ -844,6 +847,18 @@ __global__ __launch_bounds__(256) void kmeans_chunk_sum_bf16v_kernel(const bf16_
     for (int i = 0; i < 8; ++i) sm[wave][cl * 8 + i] = acc[i];
   __syncthreads();
   for (int c = threadIdx.x; c < D; c += 256) partial[b * D + c] = ((sm[0][c] + sm[1][c]) + sm[2][c]) + sm[3][c];
+}
+
+// The radix grouping's sort input: keys = the labels with every label outside [0, k) (−1: a row
+// without a winner) mapped to k, so that those rows sort behind cluster k − 1 and offsets[k] stops
+// short of them (the counting sorts of groupsort.hip drop them too); payloads = the row numbers.
+__global__ __launch_bounds__(256) void kmeans_sort_keys_kernel(const int* __restrict__ labels, long n, int k,
+                                                               int* __restrict__ keys, int* __restrict__ rows) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int l = labels[i];
+  keys[i] = (unsigned)l < (unsigned)k ? l : k;
+  rows[i] = (int)i;
 }
 
 // Cluster boundaries from the sorted labels, no host sync: offsets[c] = first position of a
@@ -1094,6 +1109,13 @@ FMLX_API int fmlx_kmeans_chunk_sum_bf16v(const void* X, long ld, int D, const in
                        (const bf16_t*)X, ld, D, order, offsets, chunk_off, k, partial);
     return (int)hipGetLastError();
   }, -2);
+}
+
+FMLX_API int fmlx_kmeans_sort_keys(const int* labels, long n, int k, int* keys, int* rows, void* stream) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(kmeans_sort_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     labels, n, k, keys, rows);
+  return (int)hipGetLastError();
 }
 
 FMLX_API int fmlx_kmeans_offsets(const int* keys_sorted, long n, int k, long* offsets, long* chunk_off, void* stream) {

@@ -252,7 +252,10 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_bf16_wide_kernel(const b
     const float kx = (lo ? ok : bk) * (1.0f / sqrtf(__shfl(x2, lane >> 1, 64)));
     bi = kx == kx ? (lo ? oi : bi) : -1;
   } else {
-    if (ok < bk || (ok == bk && oi < bi)) bi = oi;
+    const bool lo = ok < bk || (ok == bk && oi < bi);
+    // ‖x‖² is not in the key: a −inf key (x·c = +inf) means an infinite element in the row, whose
+    // distances are all inf or NaN — no winner, label 0
+    bi = (lo ? ok : bk) == -__builtin_inff() ? 0 : (lo ? oi : bi);
   }
   if (half == 0 && row0 + rho < n) labels[row0 + rho] = bi;
 }

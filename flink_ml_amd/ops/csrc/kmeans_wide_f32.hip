@@ -278,7 +278,10 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_f32_wide_kernel(const fl
     const float kx = (lo ? ok : bk) * (1.0f / sqrtf(x2));
     bi = kx == kx ? (lo ? oi : bi) : -1;
   } else {
-    if (ok < bk || (ok == bk && oi < bi)) bi = oi;
+    const bool lo = ok < bk || (ok == bk && oi < bi);
+    // ‖x‖² is not in the key: a −inf key (x·c = +inf) means an infinite element in the row, whose
+    // distances are all inf or NaN — no winner, label 0
+    bi = (lo ? ok : bk) == -__builtin_inff() ? 0 : (lo ? oi : bi);
   }
   if (h == 0 && xrow < n) labels[xrow] = bi;
 }

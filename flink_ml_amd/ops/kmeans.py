@@ -313,7 +313,9 @@ def assign(X: torch.Tensor, cb: CentroidBuffers, metric: str, out: torch.Tensor 
             Xc = X[r0:r0 + GEMM_ASSIGN_ROWS]
             # ‖c‖² − 2x·c: the per-row ‖x‖² does not move the argmin (no n×D temporary for it)
             d = torch.addmm(cn2.unsqueeze(0), Xc, C.t(), alpha=-2.0)
-            d.nan_to_num_(nan=float("inf"))  # NaN distances never win, like torch_assign / the kernels
+            # NaN distances never win, like torch_assign / the kernels; a −inf key (x·c = +inf: an
+            # infinite element in the row, whose distances with ‖x‖² are all inf or NaN) neither: label 0
+            d.nan_to_num_(nan=float("inf"), posinf=float("inf"), neginf=float("inf"))
             out[r0:r0 + Xc.shape[0]] = torch.argmin(d, dim=1).to(torch.int32)  # first (lowest) index on ties
         return out
     C = cb.cent.to(X.dtype).contiguous()
@@ -323,8 +325,17 @@ def assign(X: torch.Tensor, cb: CentroidBuffers, metric: str, out: torch.Tensor 
     return out
 
 
+def _first_strict_min(d: torch.Tensor) -> torch.Tensor:
+    """``DistanceMeasure.findClosest`` on an [n, k] distance block: the first strict minimum, a NaN
+    distance never wins (strict '<'), −1 for a row with no distance below +inf."""
+    d = torch.where(torch.isnan(d), torch.full_like(d, float("inf")), d)
+    lab = torch.argmin(d, dim=1)  # the first minimum: lowest index on ties
+    return torch.where((d < float("inf")).any(dim=1), lab, torch.full_like(lab, -1))
+
+
 def torch_assign(X: torch.Tensor, C: torch.Tensor, metric: str) -> torch.Tensor:
-    """Host reference of findClosest (EuclideanDistanceMeasure.java:53-73 incl. pruning order)."""
+    """Host reference of findClosest (EuclideanDistanceMeasure.java:53-73 incl. pruning order; the
+    other metrics DistanceMeasure.java's default: −1 for a row without a winner)."""
     X = X.to(torch.float64)
     C = C.to(device=X.device, dtype=torch.float64)
     if X.shape[0] == 0:
@@ -339,7 +350,7 @@ def torch_assign(X: torch.Tensor, C: torch.Tensor, metric: str) -> torch.Tensor:
         d = torch.cdist(X, C, p=1)
     else:
         d = 1.0 - (X @ C.T) / torch.linalg.vector_norm(X, dim=1)[:, None] / torch.linalg.vector_norm(C, dim=1)[None, :]
-    return torch.argmin(d, dim=1)
+    return _first_strict_min(d)
 
 
 class KMeansRound:
@@ -384,8 +395,9 @@ class KMeansRound:
             # sort (radix.hip, one segment) over ceil(log2 k) bits, buffers allocated once
             from . import glm as _glm
 
-            self.bits = max(1, int(k - 1).bit_length())
-            self.iota = torch.arange(self.n, dtype=torch.int32, device=dev)
+            # keys 0..k: a label outside [0, k) (−1, a row without a winner) sorts as key k, behind
+            # every cluster, and offsets[k] stops short of it (fmlx_kmeans_sort_keys)
+            self.bits = int(k).bit_length()
             self.sort_keys = torch.empty(self.n, dtype=torch.int32, device=dev)
             self.sort_vals = torch.empty(self.n, dtype=torch.int32, device=dev)
             self.sort_keys_alt = torch.empty(self.n, dtype=torch.int32, device=dev)
@@ -416,8 +428,8 @@ class KMeansRound:
         else:
             from . import glm as _glm
 
-            self.sort_keys.copy_(self.labels)
-            self.sort_vals.copy_(self.iota)
+            native.call("fmlx_kmeans_sort_keys", native.ptr(self.labels), self.n, self.k, native.ptr(self.sort_keys),
+                        native.ptr(self.sort_vals), stream)
             _glm.seg_sort(self.sort_keys, self.sort_vals, [0, self.n], [0], self.bits, self.sort_keys_alt,
                           self.sort_vals_alt, self.sort_scratch)
             # cluster boundaries on the device (no host sync: the round is hipGraph-capturable)
@@ -465,9 +477,10 @@ def torch_round_payload(X: torch.Tensor, C: torch.Tensor, metric: str) -> torch.
     if X.shape[0] == 0:
         return out
     lab = torch_assign(X, C, metric)
-    sums = torch.zeros((k, D), dtype=torch.float64).index_add_(0, lab, X)
+    ok = lab >= 0  # a row without a winner (−1) adds to no sum and no count, like the device round
+    sums = torch.zeros((k, D), dtype=torch.float64).index_add_(0, lab[ok], X[ok])
     out[: k * D] = sums.reshape(-1)
-    out[k * D:] = torch.bincount(lab, minlength=k).to(torch.float64)
+    out[k * D:] = torch.bincount(lab[ok], minlength=k).to(torch.float64)
     return out
 
 
@@ -728,7 +741,8 @@ def torch_assign_csr(X, C: torch.Tensor, metric: str) -> torch.Tensor:
     d = torch_dist_csr(X, C, metric)
     if metric == "euclidean":
         d = torch.where(torch.isnan(d), torch.full_like(d, float("inf")), d)
-    return torch.argmin(d, dim=1)
+        return torch.argmin(d, dim=1)
+    return _first_strict_min(d)
 
 
 def torch_round_payload_csr(X, C: torch.Tensor, metric: str, labels: torch.Tensor = None) -> torch.Tensor:

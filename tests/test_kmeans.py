@@ -119,6 +119,68 @@ def test_config1_plumbing_100_points_4_ranks():
             assert (x > 2.5) == (p == (1 if res[0][0][1][0] > 2.5 else 0))
 
 
+# ------------------------------------------------------------------------------------ degenerate inputs
+METRICS = ["euclidean", "manhattan", "cosine"]
+
+
+@pytest.fixture
+def cpu_context():
+    """The host path whatever the machine has (the context is reset after every test)."""
+    from flink_ml_amd.parallel import context as pctx
+
+    pctx.set_context(pctx.SPMDContext(device=torch.device("cpu")))
+
+
+@pytest.mark.parametrize("k", [5, 33])
+@pytest.mark.parametrize("metric", METRICS)
+def test_host_reference_on_degenerate_inputs(metric, k, cpu_context):
+    """torch_assign, torch_assign_csr, torch_round_payload and KMeansModel.transform on a zero row, NaN
+    and ±inf rows, a zero centroid, NaN centroids and an inf centroid against the reference of
+    tests/test_kmeans_degenerate_gpu.py: a NaN distance never wins, a row without a winner gets 0
+    under euclidean and −1 under manhattan and cosine and adds nothing to the round's payload."""
+    from flink_ml_amd.models.kmeans import kmeans_model_data_table
+    from flink_ml_amd.ops import kmeans as kk
+    from flink_ml_amd.table import SparseColumn
+    from tests import test_kmeans_degenerate_gpu as dg
+
+    D = 37
+    X, C = dg.degenerate(D, k, torch.float64, 0)
+    assert dg.separated(X, C, metric, 52)
+    ref = dg.ref_assign(X, C, metric)
+    assert ref[[7, 11, 13]].tolist() == [0 if metric == "euclidean" else -1] * 3
+    assert not bool(((ref == 1) | (ref == 2)).any()) and int(ref.max()) < k
+    assert torch.equal(kk.torch_assign(X, C, metric), ref)
+    assert torch.equal(kk.torch_assign_csr(SparseColumn.from_dense(X), C, metric), ref)
+    torch.testing.assert_close(kk.torch_round_payload(X, C, metric), dg.ref_payload(X, ref, k), rtol=1e-12,
+                               atol=1e-12, equal_nan=True)
+    model = KMeansModel().set_model_data(kmeans_model_data_table(C.numpy(), np.ones(k)))
+    model.set_k(k).set_distance_measure(metric)
+    pred = model.transform(Table({"features": X}))[0].column("prediction")
+    assert torch.equal(torch.as_tensor(pred).long(), ref)
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_cpu_lloyd_never_chooses_the_nan_centroid_of_an_empty_cluster(metric, cpu_context):
+    """Round 1 leaves cluster 2 empty (a far centroid; under cosine a zero one), the finalize turns it
+    into NaN; rounds 2 and 3 must not choose it, and the other centroids stay finite."""
+    from flink_ml_amd.models.kmeans import kmeans_lloyd
+    from tests import test_kmeans_degenerate_gpu as dg
+
+    D, k = 37, 5
+    X, C = dg.clustered(D, k, 0)
+    C[2] = 0.0 if metric == "cosine" else 100.0
+    cents, weights = kmeans_lloyd(X, C.numpy(), 3, metric)
+    assert np.isnan(cents[2]).all() and weights[2] == 0 and weights.sum() == dg.N
+    assert np.isfinite(cents[[0, 1, 3, 4]]).all()
+    for _ in range(3):
+        assert dg.separated(X, C, metric, 52)
+        lab = dg.ref_assign(X, C, metric)
+        assert not bool((lab == 2).any()) and int(lab.min()) >= 0
+        p = dg.ref_payload(X, lab, k)
+        C = p[: k * D].reshape(k, D) * (1.0 / p[k * D:])[:, None]
+    assert np.allclose(cents, C.numpy(), rtol=1e-12, atol=1e-12, equal_nan=True)
+
+
 # ------------------------------------------------------------------------------------ GPU
 @pytest.mark.gpu
 @pytest.mark.parametrize("D", [2, 10, 64, 100, 128, 200])
