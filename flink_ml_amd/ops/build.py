@@ -206,6 +206,10 @@ FILE_FLAGS = {"kmeans.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-Wno-inline-as
               # likewise, fp64 (64 accumulator registers become keys once per macro-tile)
               "knn_wide_f64.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-Wno-inline-asm",
                                    "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              # the SLP vectoriser pairs the accumulators of two rows into v_pk_add_f32 and pays a
+              # v_and per element for |x − c| (2 VALU issues per pair-element); without it the
+              # absolute value folds into the add's source modifier (1.5 with the packed difference)
+              "kmeans_l1.hip": ["-Wno-inline-asm", "-fno-slp-vectorize"],
               # the fused round's ticket atomics: no lane-0 result fix-up (keeps counted vmcnt waits)
               "glm.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
               "glm_sparse.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],

@@ -65,7 +65,7 @@ def mfma_ok(X: torch.Tensor, metric: str) -> bool:
 # bf16 rows of 256 < D <= 4096 (csrc/kmeans_wide.hip; cosine from D = 64, which has no narrow MFMA
 # kernel), fp32 rows of 128 < D <= 4096 (csrc/kmeans_wide_f32.hip) and fp64 rows of 16 <= D <= 4096
 # (csrc/kmeans_wide_f64.hip): the K-tiled MFMA assign, a euclidean and a cosine instantiation each,
-# and the wide gather-sum, which serves every metric (manhattan assigns stay on the generic kernel).
+# and the wide gather-sum, which serves every metric (manhattan assigns: csrc/kmeans_l1.hip, below).
 # FMLX_KMEANS_WIDE=0: the routes before them (bf16: an fp32 copy; then the GEMM + argmin block or
 # the wave-per-row assign; no round past D = 1024), for the A/B and the tests. =force: the fp32 and
 # fp64 assigns take the wide kernel at every shape it supports, whatever wide32_route and
@@ -92,6 +92,70 @@ def mfma_wide_f64_ok(X: torch.Tensor, metric: str) -> bool:
     return (WIDE and X.device.type == "cuda" and X.dtype == torch.float64 and metric in WIDE_METRICS
             and X.stride(1) == 1 and 16 <= X.shape[1] <= WIDE_MAX_D and X.shape[1] % 2 == 0
             and X.stride(0) % 2 == 0 and X.shape[1] <= X.stride(0) < (1 << 22) and X.data_ptr() % 16 == 0)
+
+
+# Manhattan assigns of fp32, bf16 (read as stored: no fp32 copy) and fp64 rows up to D = 4096: the
+# tiled VALU kernel of csrc/kmeans_l1.hip. FMLX_KMEANS_L1=1: where l1_route measured it ahead of the
+# generic kernels; =force: every shape it supports; =0: the generic kernels as before it.
+L1 = {"0": False, "force": "force"}.get(os.environ.get("FMLX_KMEANS_L1", "1"), True)
+L1_PIECE = {torch.float32: 4, torch.bfloat16: 8, torch.float64: 2}  # elements per 16 bytes
+
+
+def l1_ok(X: torch.Tensor, metric: str) -> bool:
+    m = L1_PIECE.get(X.dtype)
+    return bool(L1 and m and X.device.type == "cuda" and metric == "manhattan" and X.stride(1) == 1
+                and m <= X.shape[1] <= WIDE_MAX_D and X.shape[1] % m == 0 and X.stride(0) % m == 0
+                and X.shape[1] <= X.stride(0) < (1 << (22 if X.dtype == torch.float64 else 23))
+                and X.data_ptr() % 16 == 0)
+
+
+# Where the tiled kernel takes over from the generic ones: where it beat them in both run orders
+# (scripts/bench_kmeans_l1.py, profiles/r26/INDEX.md; ms per assign, new vs old; all measured). A
+# block walks its 128 rows' whole K extent for a macro-tile of 128 centroids (fp64: 64) whatever k, and
+# 1,000 rows are 8 blocks on 256 CUs: few centroids on few rows stay on the wave-per-row kernel. As
+# (fewest rows, fewest centroids, widest row) classes for D <= 1024:
+#  fp32
+#   1,000,000 rows: k = 10 wins at D = 100 (0.738 vs 0.750); k = 16 wins at 128 (0.717 vs 1.008) and loses
+#     at 512 (2.73 vs 1.95); k = 32 wins at 512 (2.73 vs 4.12) and 1024 (5.43 vs 6.85); k = 8 loses at 128
+#     (0.715 vs 0.576).
+#   100,000 rows: k = 16 wins at 128 (0.102 vs 0.106) and loses at 512 (0.383 vs 0.208); k = 32 wins at 512
+#     (0.383 vs 0.393) and loses at 1024 (0.761 vs 0.669); k = 64 wins at 1024 (0.759 vs 1.278); k = 8 loses
+#     at 128 (0.102 vs 0.060).
+#   10,000 rows: k = 64 wins at 128 (0.039 vs 0.055) and loses at 512 (0.141 vs 0.076); k = 256 at 512 and
+#     k = 1024 at 512 win in one order only (1.074 vs 1.060): not routed.
+#   1,000 rows: k = 256 wins at 128 (0.072 vs 0.075) and loses at 512 (0.272 vs 0.111); k = 64 loses at 128.
+#  bf16 (the old side starts with an fp32 copy of the matrix)
+#   1,000,000 rows: k = 8 wins at 128 (0.640 vs 0.698) and loses at 512 (2.49 vs 1.52); k = 32 wins at 512
+#     (2.49 vs 4.56) and 1024 (4.96 vs 7.70); k = 16 loses at 512 (2.50 vs 2.47).
+#   100,000 rows: k = 16 wins at 128 (0.096 vs 0.121) and loses at 512; k = 32 wins at 512 (0.365 vs 0.444)
+#     and 1024 (0.722 vs 0.765); k = 8 loses at 128 (0.096 vs 0.074).
+#   10,000 rows: k = 64 wins at 128 (0.038 vs 0.059) and loses at 512; k = 256 wins at 512 (0.276 vs 0.276
+#     at worst, 0.2757 vs 0.2760) and wins in one order only at 1024; k = 1024 wins at 1024 (2.165 vs 2.199).
+#   1,000 rows: k = 256 wins at 128 (0.072 vs 0.076) and loses at 512 (0.273 vs 0.113).
+#  fp64
+#   1,000,000 rows: k = 8 wins at 128 (0.553 vs 1.310), 512 (2.04 vs 2.53) and 1024 (4.14 vs 5.60).
+#   100,000 rows: k = 8 wins at 128 (0.080 vs 0.146) and loses at 512 (0.294 vs 0.268); k = 16 wins at 512
+#     (0.293 vs 0.466) and 1024 (0.578 vs 1.044); k = 2 loses everywhere.
+#   10,000 rows: k = 16 wins at 128 (0.032 vs 0.032 at worst, 0.0315 vs 0.0317) and loses at 512; k = 64
+#     wins at 512 (0.114 vs 0.184) and 1024 (0.223 vs 0.401); k = 32 loses at 512 and 1024.
+#   1,000 rows: k = 64 wins at 128 (0.031 vs 0.033) and loses at 512 (0.111 vs 0.046); k = 256 loses at 512.
+# Past D = 1024 the old route is the thread-per-row kernel, which lost at every measured shape in
+# every dtype (fp32, 1,000 x 2048, k = 2: 0.542 vs 0.722; 1M x 2048, k = 1024: 88.3 ms vs 18.2 s).
+L1_CLASSES = {
+    torch.float32: ((1_000_000, 10, 100), (1_000_000, 32, 1024), (100_000, 16, 128), (100_000, 32, 512),
+                    (100_000, 64, 1024), (10_000, 64, 128), (1_000, 256, 128)),
+    torch.bfloat16: ((1_000_000, 8, 128), (1_000_000, 32, 1024), (100_000, 16, 128), (100_000, 32, 1024),
+                     (10_000, 64, 128), (10_000, 256, 512), (10_000, 1024, 1024), (1_000, 256, 128)),
+    torch.float64: ((1_000_000, 8, 1024), (100_000, 8, 128), (100_000, 16, 1024), (10_000, 16, 128),
+                    (10_000, 64, 1024), (1_000, 64, 128)),
+}
+
+
+def l1_route(n: int, D: int, k: int, dtype) -> bool:
+    """Whether ``assign`` sends a shape that ``l1_ok`` accepts to the tiled manhattan kernel."""
+    if L1 == "force" or D > 1024:
+        return True
+    return any(n >= nmin and k >= kmin and D <= dmax for nmin, kmin, dmax in L1_CLASSES.get(dtype, ()))
 
 
 class CentroidBuffers:
@@ -277,9 +341,17 @@ def assign(X: torch.Tensor, cb: CentroidBuffers, metric: str, out: torch.Tensor 
         native.call("fmlx_kmeans_assign_bf16_wide" + cos, native.ptr(X), X.stride(0), n, D, native.ptr(cb.Cb), cb.DP,
                     native.ptr(cb.cnorm_b), cb.kpad, native.ptr(out), native.stream_ptr(X.device))
         return out
+    if X.dtype == torch.bfloat16 and l1_ok(X, metric) and l1_route(n, D, cb.k, X.dtype):
+        # the rows as they are stored: no fp32 copy of the matrix (csrc/kmeans_l1.hip)
+        return _assign_l1("fmlx_kmeans_assign_l1_bf16", X, cb.cent if cb.cent.dtype == torch.float32 else cb.cent.to(torch.float32), cb.k, out)
     if X.dtype not in (torch.float32, torch.float64):
         X = X.to(torch.float32)
     X = X if X.stride(1) == 1 else X.contiguous()
+    if X.dtype != torch.bfloat16 and l1_ok(X, metric) and l1_route(n, D, cb.k, X.dtype):
+        # Σ|x − c| in the rows' dtype with the argmin in registers (csrc/kmeans_l1.hip); centroid
+        # buffers of the other width are converted once per call, as the generic route does
+        entry = "fmlx_kmeans_assign_l1_f32" if X.dtype == torch.float32 else "fmlx_kmeans_assign_l1_f64"
+        return _assign_l1(entry, X, cb.cent.to(X.dtype), cb.k, out)
     if mfma_wide_f32_ok(X, metric) and wide32_route(n, D, cb.k, metric):
         # fp32 MFMA keys ‖c‖² − 2·x·c with the argmin in registers (csrc/kmeans_wide_f32.hip); an
         # fp64 centroid matrix is converted once per call, as the generic route does
@@ -322,6 +394,12 @@ def assign(X: torch.Tensor, cb: CentroidBuffers, metric: str, out: torch.Tensor 
     cn = cb.cnorm.to(X.dtype).contiguous()
     native.call("fmlx_kmeans_assign_generic", native.dtype_code(X.dtype), native.ptr(X), X.stride(0), n, D,
                 native.ptr(C), native.ptr(cn), cb.k, METRICS[metric], native.ptr(out), native.stream_ptr(X.device))
+    return out
+
+
+def _assign_l1(entry: str, X: torch.Tensor, C: torch.Tensor, k: int, out: torch.Tensor) -> torch.Tensor:
+    native.call(entry, native.ptr(X), X.stride(0), X.shape[0], X.shape[1], native.ptr(C),
+                C.stride(0), k, native.ptr(out), native.stream_ptr(X.device))
     return out
 
 
