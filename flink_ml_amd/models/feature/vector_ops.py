@@ -14,6 +14,7 @@ from typing import List
 import numpy as np
 import torch
 
+from ... import config
 from ...ops import blas, native
 
 from ...api.stage import Transformer
@@ -288,8 +289,32 @@ class PolynomialExpansion(Transformer, HasInputCol, HasOutputCol):
 class Interaction(Transformer, HasInputCols, HasOutputCol):
     JAVA_CLASS_NAME = "org.apache.flink.ml.feature.interaction.Interaction"
 
+    def _transform_csr(self, t):
+        """The output column from the CSR route (``blas.interaction_csr``: a sparse input is never
+        densified), or None when the route is not taken or refuses. The values reach the kernels
+        as the dense route converts them (the compute device's dtype), so both routes have the
+        same dense image."""
+        names = self.get(self.INPUT_COLS)
+        if not any(t.is_sparse(c) for c in names):
+            return None
+        width = math.prod(t.vector_size(c) for c in names)
+        take, max_density = blas.interaction_csr_route(t.num_rows, width, config.compute_device())
+        if not take:
+            return None
+        cols = []
+        for c in names:
+            col = t.column(c)
+            if isinstance(col, torch.Tensor) and col.dim() == 1:
+                cols.append(col.to(device=config.compute_device(), dtype=torch.float64))
+            else:
+                cols.append(vector_input(t, c) if t.is_sparse(c) else dense_input(t, c))
+        return blas.interaction_csr(cols, max_density=max_density)
+
     def transform(self, *inputs):
         t = inputs[0]
+        out = self._transform_csr(t)
+        if out is not None:
+            return [t.with_column(self.get(self.OUTPUT_COL), out)]
         mats = []
         sparse = False
         for c in self.get(self.INPUT_COLS):

@@ -18,12 +18,15 @@ fp64 for fp64 rows.
 ``hDot``                     ``hdot(v, X)`` (dense or CSR rows ∘ one vector)
 ``gemv(…, trans)``           ``gemv`` (N) / ``gemv_t(X, m)`` (Xᵀ·m, deterministic column sums)
 (Normalizer map)             ``normalize(X, p)`` (norm + scale fused, one pass per row)
+(Interaction map)            ``interaction(mats)`` (dense), ``interaction_csr(cols)`` (a sparse
+                             input: CSR to CSR, ``csrc/interaction_csr.hip``)
 ===========================  ========================================================
 """
 from __future__ import annotations
 
 import ctypes
 import math
+import os
 from typing import Optional, Sequence
 
 import torch
@@ -342,3 +345,168 @@ def interaction(mats: Sequence[torch.Tensor]) -> torch.Tensor:
     for m in mats[1:]:
         out = (out[:, :, None] * m[:, None, :]).reshape(n, -1)
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Interaction with sparse inputs (csrc/interaction_csr.hip): CSR in, CSR out, no [n, Π D_c] matrix
+# ---------------------------------------------------------------------------------------------
+# FMLX_INTERACTION_CSR: "0" = sparse inputs are densified, crossed by ``interaction`` and turned back
+# into CSR (the route before the CSR kernels), "1" = the CSR route whenever it does not refuse,
+# "auto" = the CSR route when the dense fp64 [n, Π D_c] intermediate would exceed the HBM budget or
+# the output's density total / (n · Π D_c) is at most INTERACTION_CSR_CROSSOVER.
+INTERACTION_CSR_ROUTE = os.environ.get("FMLX_INTERACTION_CSR", "auto")
+# the highest output density of the measured sweep (100,000 rows of sparse(64) × sparse(64), output
+# densities 0.25 % … 100 %; scripts/bench_interaction_sparse.py, profiles/r27/INDEX.md) at which the
+# CSR route beat the densifying one in both run orders: it won at every density, at 100 % (every
+# cell non-zero) with 6.44 / 6.44 ms against 92.8 / 90.7 ms, so "auto" takes it for every sparse
+# input it does not refuse. None would mean: the budget rule alone.
+INTERACTION_CSR_CROSSOVER: Optional[float] = 1.0
+INTERACTION_CSR_CHUNK = 4096     # output entries per block of the emit kernel
+INTERACTION_CSR_MAX_COLS = 8
+_IC_LIMIT = 2 ** 31              # Π D_c, a row's entries and all entries stay below this
+IC_ERR_RANGE, IC_ERR_ROUTE, IC_ERR_LONG = 1, 2, 4  # csrc/interaction_csr.hip's error word
+
+
+def interaction_csr_route(n: int, width: int, device):
+    """(take, max_density) for ``Interaction`` with a sparse input (``INTERACTION_CSR_ROUTE``):
+    whether to try ``interaction_csr``, and the output density above which it is to refuse (None:
+    none)."""
+    if INTERACTION_CSR_ROUTE == "0":
+        return False, None
+    if INTERACTION_CSR_ROUTE == "1":
+        return True, None
+    device = torch.device(device)
+    if device.type == "cuda":
+        from ..common.outofcore import hbm_budget
+
+        budget = hbm_budget(device)
+        if budget is not None and n * width * 8 > budget:
+            return True, None
+    return INTERACTION_CSR_CROSSOVER is not None, INTERACTION_CSR_CROSSOVER
+
+
+def _ic_columns(cols):
+    """The columns as SparseColumn / [n, d] tensors, and (n, [D_c])."""
+    out = []
+    for c in cols:
+        if not isinstance(c, SparseColumn):
+            c = c[:, None] if c.dim() == 1 else c
+        out.append(c)
+    n = len(out[0]) if isinstance(out[0], SparseColumn) else out[0].shape[0]
+    return out, n, [c.size if isinstance(c, SparseColumn) else int(c.shape[1]) for c in out]
+
+
+def _ic_torch(cols, n: int, dims, width: int, max_density):
+    """``interaction_csr`` in torch: every column's non-zero entries as a compacted CSR list, the
+    output positions expanded with ``repeat_interleave`` and decoded in mixed radix."""
+    dev = cols[0].values.device if isinstance(cols[0], SparseColumn) else cols[0].device
+    lists = []  # per column: (non-zeros per row, first list entry per row, indices, values)
+    length = torch.ones(n, dtype=torch.int64, device=dev)
+    for c, D in zip(cols, dims):
+        if isinstance(c, SparseColumn):
+            idx, v = c.indices.to(torch.int64), c.values.to(torch.float64)
+            if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= D):
+                raise ValueError("sparse feature index out of range [0, size)")
+            ptr = c.indptr.to(torch.int64)
+            rows = torch.repeat_interleave(torch.arange(n, device=dev), ptr[1:] - ptr[:-1])
+            if idx.numel() > 1 and bool(((rows[1:] == rows[:-1]) & (idx[1:] <= idx[:-1])).any()):
+                return None  # unsorted, or an index stored twice
+        else:
+            v = c.to(torch.float64).reshape(-1)
+            rows = torch.repeat_interleave(torch.arange(n, device=dev), D)
+            idx = torch.arange(D, device=dev).repeat(n)
+        if not bool(torch.isfinite(v).all()):
+            return None
+        keep = v != 0
+        k = torch.bincount(rows[keep], minlength=n)
+        lists.append((k, torch.cumsum(k, 0) - k, idx[keep], v[keep]))
+        length = torch.clamp(length * k, max=_IC_LIMIT)
+    total = int(length.sum())
+    if (n and int(length.max()) >= _IC_LIMIT) or total >= _IC_LIMIT:
+        return None
+    if max_density is not None and total > max_density * n * width:
+        return None
+    indptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    indptr[1:] = torch.cumsum(length, 0)
+    orow = torch.repeat_interleave(torch.arange(n, device=dev), length)
+    x = torch.arange(total, device=dev) - indptr[orow]
+    value = torch.ones(total, dtype=torch.float64, device=dev)
+    index = torch.zeros(total, dtype=torch.int64, device=dev)
+    stride = 1
+    for (k, first, idx, v), D in zip(reversed(lists), reversed(dims)):  # the last column: fastest digit, first factor
+        kk = k[orow]
+        e = first[orow] + x % kk
+        x = x // kk
+        value = value * v[e]
+        index += idx[e] * stride
+        stride *= D
+    return SparseColumn(indptr, index.to(torch.int32), value, width)
+
+
+def interaction_csr(cols, chunk: int = INTERACTION_CSR_CHUNK, max_density: Optional[float] = None):
+    """Interaction of up to 8 columns (``SparseColumn``, dense [n, d] or scalar [n] tensors) as a
+    ``SparseColumn`` of size Π D_c, without the dense [n, Π D_c] matrix. Row r holds one entry per
+    combination of one non-zero (not ±0) entry from every column: index Σ idx_c · Π_{c' > c} D_c'
+    (first column slowest), value the fp64 product 1.0 · v_last · … · v_first, ascending. A product
+    of non-zero factors that underflows stays a stored 0.0 (``SparseColumn.from_dense`` of the
+    dense result would drop it).
+
+    Returns None (the caller keeps the dense route) for: no or more than 8 columns, Π D_c ≥ 2^31,
+    a row or a result of 2^31 or more entries, a non-finite value (the dense result has NaN where
+    a sparse row stores nothing), a sparse row whose indices do not strictly ascend, or — with
+    ``max_density`` — more than max_density · n · Π D_c entries. An index outside [0, D_c) raises.
+    On a GPU: ``csrc/interaction_csr.hip`` (``chunk``: output entries per block of the emit pass,
+    which does not change the result); on the CPU a torch formulation of the same definition."""
+    if not 1 <= len(cols) <= INTERACTION_CSR_MAX_COLS:
+        return None
+    cols, n, dims = _ic_columns(cols)
+    width = math.prod(dims)
+    if min(dims) < 1 or width >= _IC_LIMIT or n >= _IC_LIMIT:
+        return None
+    dev = cols[0].values.device if isinstance(cols[0], SparseColumn) else cols[0].device
+    if dev.type != "cuda" or n == 0:
+        return _ic_torch(cols, n, dims, width, max_density)
+    m = len(cols)
+    keep, ptrs, idxs, vals, lds, f64 = [], [], [], [], [], []
+    for c in cols:
+        if isinstance(c, SparseColumn):
+            ip, ix, v = _csr_dev(c)
+            keep += [ip, ix, v]
+            ptrs.append(ip.data_ptr())
+            idxs.append(ix.data_ptr())
+            lds.append(0)
+        else:
+            v = c if c.dtype in (torch.float32, torch.float64) else c.to(
+                torch.float32 if c.dtype == torch.bfloat16 else torch.float64)
+            v = v if v.stride(1) == 1 or v.shape[1] == 1 else v.contiguous()
+            keep.append(v)
+            ptrs.append(None)
+            idxs.append(None)
+            lds.append(v.stride(0))
+        vals.append(v.data_ptr())
+        f64.append(int(v.dtype == torch.float64))
+    args = (m, ctypes.cast((ctypes.c_void_p * m)(*ptrs), ctypes.c_void_p),
+            ctypes.cast((ctypes.c_void_p * m)(*idxs), ctypes.c_void_p),
+            ctypes.cast((ctypes.c_void_p * m)(*vals), ctypes.c_void_p),
+            ctypes.cast((ctypes.c_long * m)(*lds), ctypes.c_void_p),
+            ctypes.cast((ctypes.c_long * m)(*dims), ctypes.c_void_p),
+            ctypes.cast((ctypes.c_int * m)(*f64), ctypes.c_void_p), n)
+    cnt = torch.empty((n, m), dtype=torch.int32, device=dev)
+    length = torch.empty(n, dtype=torch.int64, device=dev)
+    scratch = torch.empty(int(native.kernels().fmlx_interaction_csr_scratch(n)), dtype=torch.int64, device=dev)
+    indptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    state = native.zeros(2, torch.int64, dev)
+    native.call("fmlx_interaction_csr_count", *args, native.ptr(cnt), native.ptr(length), native.ptr(scratch),
+                native.ptr(indptr), native.ptr(state), native.stream_ptr(dev))
+    from ..utils import hostsync
+
+    total, err = hostsync.to_host(state).tolist()  # the one wait on the device: it sizes the output
+    if err & IC_ERR_RANGE:
+        raise ValueError("sparse feature index out of range [0, size)")
+    if err or total >= _IC_LIMIT or (max_density is not None and total > max_density * n * width):
+        return None
+    index = torch.empty(total, dtype=torch.int32, device=dev)
+    value = torch.empty(total, dtype=torch.float64, device=dev)
+    native.call("fmlx_interaction_csr_emit", *args, native.ptr(cnt), native.ptr(indptr), total, int(chunk),
+                native.ptr(index), native.ptr(value), native.stream_ptr(dev))
+    return SparseColumn(indptr, index, value, width)
